@@ -42,7 +42,7 @@ def main():
     os.environ["TMPDIR"] = "/tmp"
     work = os.path.join("/tmp", "prof_%s_%s" % (tag, name))
     shutil.rmtree(work, ignore_errors=True)
-    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(STEPS), "--warmup", str(WARMUP), "--cpu-seconds", "0"] + bargs
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(STEPS), "--warmup", str(WARMUP), "--full", "--cpu-seconds", "0"] + bargs
     r = run(["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", work + "/trace", "--"] + bench)
     line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1]
     open(os.path.join(out, "%s_%s_bench.json" % (tag, name)), "w").write(line + "\n")

@@ -23,7 +23,7 @@ def main():
                 work = "/tmp/pmc_probe"
                 shutil.rmtree(work, ignore_errors=True)
                 cmd = ["rocprofv3", "--kernel-trace", "--pmc"] + g.split() + ["--output-format", "csv", "-d", work, "--",
-                       sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-seconds", "0", "--no-extras", "--no-verify", "--tuning-build"] + bargs
+                       sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-seconds", "0", "--no-extras", "--no-verify", "--tuning-build"] + bargs
                 print("run:", v, "|", g, flush=True)
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, env=env, cwd="/tmp", timeout=150)

@@ -286,7 +286,7 @@ def test_bench_launcher_with_two_ranks_on_one_device():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo", "--scaling", "strong",
-           "--method", "bicubic", "--nz", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"]
+           "--method", "bicubic", "--nz", "8", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1]
@@ -295,6 +295,58 @@ def test_bench_launcher_with_two_ranks_on_one_device():
     assert d["verified_slices"] == [0, 1, 3] and d["verified_all_slices_vs_gather"] is True  # rank 0's block; a failure on any rank exits 1
     assert d["gather"]["write_back_verified"] is True
     assert d["value"] > 0 and d["roofline"]["frac"] > 0
+
+
+def test_bench_plain_run_dumps_what_the_timed_launch_computed(fa, tmp_path):
+    """bench.py without --full prints the headline line alone; --dump-outputs writes the last timed launch's output slices 0 and
+    nz-1 whole and a seeded sample of the batch (float32 values, float64 flat indices), each with the positions of its undefined
+    cells, all finite, in under 64 MB, the same in two runs.  Slice 0 is the oracle's regrid of the bench's first input slice on
+    the positions of the bench's own plan build."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import torch
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    nz = 8
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--nz", str(nz), "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith('{"metric"')][-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Mcells/s"
+        assert d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert not {"roofline", "verified_slices", "cpu_baseline", "single_slice_warm"} & set(d)
+        names = sorted(os.listdir(out))
+        assert names == ["output_first_slice.npy", "output_first_slice_undefined.npy", "output_last_slice.npy", "output_last_slice_undefined.npy",
+                         "output_sample.npy", "output_sample_index.npy", "output_sample_undefined.npy"]
+        assert sum(os.path.getsize(out / n) for n in names) <= 64 << 20
+        dumps.append({n[:-4]: np.load(out / n) for n in names})
+    a, b = dumps
+    for k in a:
+        assert a[k].dtype == (np.float64 if k.endswith(("_index", "_undefined")) else np.float32)
+        assert np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
+    for k in ("output_first_slice", "output_last_slice", "output_sample"):  # the arrays as the launch wrote them, NaN where undefined
+        u = a.pop(k + "_undefined").astype(np.int64)
+        assert u.size > 0 and np.all(np.diff(u) > 0) and u[-1] < a[k].size and np.all(a[k].reshape(-1)[u] == 0)
+        a[k].reshape(-1)[u] = np.nan
+    wl = workloads.BilinearRotatedPole()
+    layer = wl.outX * wl.outY
+    assert a["output_first_slice"].shape == (wl.outY, wl.outX)
+    idx = a["output_sample_index"].astype(np.int64)
+    assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < nz * layer and a["output_sample"].shape == idx.shape
+    for k, name in ((0, "output_first_slice"), (nz - 1, "output_last_slice")):
+        at = idx[(idx >= k * layer) & (idx < (k + 1) * layer)]
+        assert at.size > 0
+        assert cases.same(a["output_sample"][np.isin(idx, at)], a[name].reshape(-1)[at - k * layer])
+    _, px, py = bench.build_plan(fa, torch, wl, fa.BILINEAR, torch.cuda.current_stream().cuda_stream)
+    want = oracle.interpolate_values(oracle.BILINEAR, px, py, wl.base_field()[None], wl.inX, wl.inY, wl.outX, wl.outY, nthreads=16)[0]
+    assert cases.same(a["output_first_slice"], want), cases.describe_mismatch(a["output_first_slice"], want)
 
 
 @pytest.mark.parametrize("method", [oracle.BILINEAR, oracle.NEAREST])
