@@ -1,5 +1,6 @@
-// Host-side geometry of the creep fill by rectangles (fill.hip, run_creepfill): pure C++, no device code -- tests/test_creep_rects.py
-// compiles it on its own and checks its invariants on random masks.
+// Host-side geometry of the fills by rectangles (fill_rects.hip, run_creepfill and run_fill2d): pure C++, no device code --
+// tests/test_creep_rects.py compiles it on its own and checks its invariants on random masks.  Line numbers such as :1266-1269 are
+// those of the reference's src/interpolation.c.
 #pragma once
 
 #include <algorithm>
@@ -94,6 +95,66 @@ inline bool slice_rects(const uint32_t* bits, uint32_t nx, uint32_t ny, uint32_t
     size_t area = 0;
     for (const Rect& r : rects) area += (size_t)(r.xb - r.xa + 1) * (r.yb - r.ya + 1);
     return !rects.empty() && rects.size() <= 64 && area * 2 <= (size_t)nx * ny;
+}
+
+// ---- what the drivers in fill_rects.hip do with the rectangles
+
+// Is the slice with these undefined cells per row (and, fill2d, defined cells that hold -0.0 or an infinity: `special`, may be
+// null) a candidate?  0: nothing to fill or nothing defined, the slice is left alone (:1266-1269, :1384-1386); -1: holes scattered
+// over (nearly) all rows leave nothing to cut, or a special cell forbids it; 1: look for rectangles
+inline int slice_candidate(const uint32_t* rowCount, const uint32_t* special, size_t ny, size_t total)
+{
+    size_t dirtyRows = 0, undefined = 0, specials = 0;
+    for (size_t y = 0; y < ny; ++y) {
+        dirtyRows += rowCount[y] != 0;
+        undefined += rowCount[y];
+        if (special) specials += special[y];
+    }
+    if (undefined == 0 || undefined == total) return 0;
+    return (dirtyRows * 10 > ny * 9 || specials != 0) ? -1 : 1;
+}
+
+// fill2d pads the rectangles of a slice to one box size
+inline void box_size(const std::vector<Rect>& rects, size_t& mw, size_t& mh)
+{
+    mw = mh = 0;
+    for (const Rect& r : rects) { mw = std::max<size_t>(mw, r.xb - r.xa + 1); mh = std::max<size_t>(mh, r.yb - r.ya + 1); }
+}
+// ... which is worth it while the boxes cover at most half of the slice
+inline bool padded_boxes_worth_it(const std::vector<Rect>& rects, size_t total)
+{
+    size_t mw, mh;
+    box_size(rects, mw, mh);
+    return rects.size() * mw * mh * 2 <= total;
+}
+// where rectangle q sits in its box of mw x mh cells: a side on the field's far border stays on the box's border (its cells are
+// the ones :1363-1370 work on); one that spans the field has both borders on the box's, being as wide as box_size's box
+inline std::pair<uint32_t, uint32_t> box_offset(const Rect& q, size_t nx, size_t ny, size_t mw, size_t mh)
+{
+    const size_t w = q.xb - q.xa + 1, h = q.yb - q.ya + 1;
+    return {(q.xb == nx - 1 && q.xa != 0) ? (uint32_t)(mw - w) : 0u, (q.yb == ny - 1 && q.ya != 0) ? (uint32_t)(mh - h) : 0u};
+}
+// end (exclusive) of the run of consecutive slices from z0 with the same rectangles and the same `skip`, at most `most` slices
+// (masks usually do not change from slice to slice)
+inline size_t same_rects_run(const std::vector<std::vector<Rect>>& rects, const std::vector<unsigned char>& skip, size_t z0, size_t most)
+{
+    size_t z1 = z0 + 1;
+    while (z1 < rects.size() && z1 - z0 < most && rects[z1] == rects[z0] && skip[z1] == skip[z0]) ++z1;
+    return z1;
+}
+// the rectangles grouped by size, groups in the order of their first member, members in their own order
+inline std::vector<std::vector<Rect>> rects_by_size(const std::vector<Rect>& rects)
+{
+    std::vector<std::vector<Rect>> groups;
+    std::vector<char> done(rects.size(), 0);
+    for (size_t i = 0; i < rects.size(); ++i) {
+        if (done[i]) continue;
+        const uint32_t w = rects[i].xb - rects[i].xa, h = rects[i].yb - rects[i].ya;
+        groups.emplace_back();
+        for (size_t j = i; j < rects.size(); ++j)
+            if (!done[j] && rects[j].xb - rects[j].xa == w && rects[j].yb - rects[j].ya == h) { groups.back().push_back(rects[j]); done[j] = 1; }
+    }
+    return groups;
 }
 
 }  // namespace creep_rects

@@ -204,7 +204,7 @@ void launch_coord_nearest(double* d_pointsX, double* d_pointsY, size_t nPoints, 
 void launch_coord_kdtree(double maxDist, double* d_pointsX, double* d_pointsY, size_t nPoints, const double* d_lon, const double* d_lat,
                          size_t orgX, size_t orgY, hipStream_t stream);
 
-// fill.hip
+// fill_rects.hip (the fills, whole or by rectangles) and fill_sum.hip (run_scan_sum)
 void run_fill2d(size_t nx, size_t ny, size_t nz, float* d_field, float relaxCrit, float corrEff, size_t maxLoop,
                 size_t* h_nChanged, hipStream_t stream);
 void run_creepfill(size_t nx, size_t ny, size_t nz, float* d_field, bool useDefault, float defaultVal,

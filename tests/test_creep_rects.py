@@ -1,7 +1,9 @@
-"""The geometry of the creep fill by rectangles (fimex_amd/csrc/creep_rects.hpp, used by run_creepfill in fill.hip) is host code: compiled
-here on its own with g++ and checked on random masks.  What run_creepfill relies on: every undefined cell lies in exactly one rectangle;
-a rectangle's outermost rows and columns hold no undefined cell unless they are the field's own border; rectangles are at least four
-cells each way where the field allows."""
+"""The geometry of the fills by rectangles (fimex_amd/csrc/creep_rects.hpp, used by run_creepfill and run_fill2d in fill_rects.hip) is host
+code: compiled here on its own with g++ and checked on random masks.  What the drivers rely on: every undefined cell lies in exactly one
+rectangle; a rectangle's outermost rows and columns hold no undefined cell unless they are the field's own border; rectangles are at least
+four cells each way where the field allows.  And of what the drivers do with the rectangles: slices are grouped in maximal runs of equal
+rectangles, rectangles by size without losing or reordering any, and a rectangle padded to its slice's box keeps every side that lies on
+the field's border on the box's border."""
 import ctypes
 import os
 import subprocess
@@ -25,6 +27,46 @@ extern "C" int creep_rects_of(uint32_t nx, uint32_t ny, uint32_t words, const ui
     }
     return n;
 }
+using fimex_amd::creep_rects::Rect;
+static std::vector<Rect> rects_from(const uint32_t* r, int n)
+{
+    std::vector<Rect> v;
+    for (int i = 0; i < n; ++i) v.push_back(Rect{r[4 * i], r[4 * i + 1], r[4 * i + 2], r[4 * i + 3]});
+    return v;
+}
+extern "C" int creep_candidate(const uint32_t* rowCount, const uint32_t* special, uint32_t ny, uint64_t total)
+{
+    return fimex_amd::creep_rects::slice_candidate(rowCount, special, ny, total);
+}
+// out: box_size's mw, mh, boxes worth it, then (ox, oy) per rectangle
+extern "C" void creep_boxes(const uint32_t* r, int n, uint32_t nx, uint32_t ny, uint64_t* out)
+{
+    namespace cr = fimex_amd::creep_rects;
+    const std::vector<Rect> v = rects_from(r, n);
+    size_t mw, mh;
+    cr::box_size(v, mw, mh);
+    out[0] = mw; out[1] = mh;
+    out[2] = cr::padded_boxes_worth_it(v, (size_t)nx * ny);
+    for (int i = 0; i < n; ++i) { const auto o = cr::box_offset(v[i], nx, ny, mw, mh); out[3 + 2 * i] = o.first; out[4 + 2 * i] = o.second; }
+}
+// slices [nz] with counts[z] rectangles each, flat in r
+extern "C" uint64_t creep_same_run(const uint32_t* r, const int* counts, const unsigned char* skip, int nz, uint64_t z0, uint64_t most)
+{
+    std::vector<std::vector<Rect>> all;
+    for (int z = 0; z < nz; ++z) { all.push_back(rects_from(r, counts[z])); r += 4 * counts[z]; }
+    return fimex_amd::creep_rects::same_rects_run(all, std::vector<unsigned char>(skip, skip + nz), z0, most);
+}
+// out: the rectangles group after group; sizes: members per group; returns the number of groups
+extern "C" int creep_by_size(const uint32_t* r, int n, uint32_t* out, int* sizes)
+{
+    const auto groups = fimex_amd::creep_rects::rects_by_size(rects_from(r, n));
+    int g = 0;
+    for (const auto& grp : groups) {
+        sizes[g++] = (int)grp.size();
+        for (const Rect& q : grp) { *out++ = q.xa; *out++ = q.xb; *out++ = q.ya; *out++ = q.yb; }
+    }
+    return g;
+}
 """
 
 
@@ -36,7 +78,13 @@ def lib():
         f.write(WRAPPER)
     so = os.path.join(d, "libcreep_rects.so")
     subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-I", os.path.join(ROOT, "fimex_amd", "csrc"), src, "-o", so], check=True)
-    return ctypes.CDLL(so)
+    lib = ctypes.CDLL(so)
+    lib.creep_same_run.restype = ctypes.c_uint64
+    lib.creep_same_run.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64]
+    lib.creep_candidate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64]
+    lib.creep_boxes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    lib.creep_by_size.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    return lib
 
 
 def rects_of(lib, mask):
@@ -125,3 +173,99 @@ def test_rectangles_of_the_usual_shapes(lib):
     rects, worth = rects_of(lib, m)
     check(m, rects)
     assert worth and sorted(rects) == sorted([(0, 20, 0, 30), (39, 80, 49, 60), (44, 90, 60, 70)])
+
+
+def random_rects(rng, nx, ny, n):
+    """rectangles as slice_rects may return them (inclusive, inside the field), with sizes and border contacts that repeat"""
+    out = []
+    for _ in range(n):
+        w, h = int(rng.choice([4, 7, 20, nx // 2, nx])), int(rng.choice([4, 9, 20, ny // 2, ny]))
+        xa = int(rng.choice([0, nx - w, rng.integers(0, nx - w + 1)]))
+        ya = int(rng.choice([0, ny - h, rng.integers(0, ny - h + 1)]))
+        out.append((xa, xa + w - 1, ya, ya + h - 1))
+    return out
+
+
+def flat(rects):
+    return np.array(rects, dtype=np.uint32).reshape(-1).copy()
+
+
+def test_rectangles_by_size_keep_every_rectangle_and_its_order(lib):
+    rng = np.random.default_rng(11)
+    for trial in range(200):
+        rects = random_rects(rng, 300, 200, int(rng.integers(0, 20)))
+        out, sizes = np.zeros(4 * max(1, len(rects)), np.uint32), np.zeros(max(1, len(rects)), np.int32)
+        ng = lib.creep_by_size(flat(rects).ctypes.data, len(rects), out.ctypes.data, sizes.ctypes.data)
+        assert sizes[:ng].sum() == len(rects) and (sizes[:ng] > 0).all()
+        got = [tuple(int(v) for v in out[4 * k:4 * k + 4]) for k in range(len(rects))]
+        groups, k = [], 0
+        for g in range(ng):
+            groups.append(got[k:k + sizes[g]]); k += sizes[g]
+        size = lambda q: (q[1] - q[0], q[3] - q[2])
+        assert all(len({size(q) for q in grp}) == 1 for grp in groups)               # one size per group
+        assert len({size(grp[0]) for grp in groups}) == ng                           # and one group per size
+        want = {}
+        for q in rects: want.setdefault(size(q), []).append(q)                       # dicts keep the order of first appearance
+        assert groups == list(want.values())
+
+
+def test_runs_of_slices_with_the_same_rectangles_are_maximal(lib):
+    rng = np.random.default_rng(12)
+    pool = [random_rects(rng, 300, 200, n) for n in (0, 1, 1, 3, 5)]
+    for trial in range(200):
+        nz = int(rng.integers(1, 12))
+        pick = np.sort(rng.integers(0, len(pool), nz)) if rng.random() < 0.5 else rng.integers(0, len(pool), nz)
+        slices = [pool[i] for i in pick]
+        skip = (rng.random(nz) < 0.2).astype(np.uint8)
+        counts = np.array([len(r) for r in slices], np.int32)
+        r = flat([q for sl in slices for q in sl] or [(0, 0, 0, 0)])
+        most = int(rng.integers(1, nz + 2))
+        z0, seen = 0, 0
+        while z0 < nz:
+            z1 = int(lib.creep_same_run(r.ctypes.data, counts.ctypes.data, skip.ctypes.data, nz, z0, most))
+            assert z0 < z1 <= nz and z1 - z0 <= most
+            assert all(slices[z] == slices[z0] and skip[z] == skip[z0] for z in range(z0, z1))
+            assert z1 == nz or z1 - z0 == most or slices[z1] != slices[z0] or skip[z1] != skip[z0]
+            seen += z1 - z0
+            z0 = z1
+        assert seen == nz  # the runs tile the batch
+
+
+def test_padded_rectangles_keep_their_border_sides_on_the_box_border(lib):
+    """In the box box_size gives, every side of a rectangle that lies on the field's border lies on the box's border (the cells the
+    border pass of the sweeps works on); a rectangle that spans the field is as wide as the widest can be, so both of its sides do."""
+    nx, ny = 300, 200
+    rng = np.random.default_rng(13)
+    spanning = 0
+    for trial in range(400):
+        rects = random_rects(rng, nx, ny, int(rng.integers(1, 8)))
+        out = np.zeros(3 + 2 * len(rects), np.uint64)
+        lib.creep_boxes(flat(rects).ctypes.data, len(rects), nx, ny, out.ctypes.data)
+        mw, mh, worth = (int(v) for v in out[:3])
+        assert mw == max(q[1] - q[0] + 1 for q in rects) and mh == max(q[3] - q[2] + 1 for q in rects)
+        assert bool(worth) == (len(rects) * mw * mh * 2 <= nx * ny)
+        for k, (xa, xb, ya, yb) in enumerate(rects):
+            w, h, ox, oy = xb - xa + 1, yb - ya + 1, int(out[3 + 2 * k]), int(out[4 + 2 * k])
+            assert ox + w <= mw and oy + h <= mh                                   # inside the box
+            assert (xa != 0 or ox == 0) and (ya != 0 or oy == 0)                   # near border of the field: near border of the box
+            assert (xb != nx - 1 or ox + w == mw) and (yb != ny - 1 or oy + h == mh)  # far border likewise
+            if xa != 0 and xb != nx - 1: assert ox == 0
+            if ya != 0 and yb != ny - 1: assert oy == 0
+            spanning += (xa == 0 and xb == nx - 1) or (ya == 0 and yb == ny - 1)
+    assert spanning > 50
+
+
+def test_slice_candidates_follow_the_dirty_row_rule(lib):
+    rng = np.random.default_rng(14)
+    nx = 50
+    for trial in range(300):
+        ny = int(rng.integers(1, 60))
+        rows = (rng.integers(0, nx + 1, ny) * (rng.random(ny) < rng.random())).astype(np.uint32)
+        if trial % 7 == 0: rows[:] = nx
+        special = (rng.integers(0, 3, ny) * (rng.random(ny) < 0.05)).astype(np.uint32) if trial % 2 else None
+        got = lib.creep_candidate(rows.ctypes.data, special.ctypes.data if special is not None else None, ny, nx * ny)
+        undefined, dirty = int(rows.sum()), int((rows != 0).sum())
+        if undefined == 0 or undefined == nx * ny:
+            assert got == 0
+        else:
+            assert got == (-1 if dirty * 10 > ny * 9 or (special is not None and special.sum() != 0) else 1)
