@@ -53,6 +53,19 @@ class Process2d(ctypes.Structure):
 
 PROCESS_FILL2D, PROCESS_CREEPFILL2D, PROCESS_CREEPFILLVAL2D = 1, 2, 3
 
+# mifi_vertical_interpol_method (include/fimex/mifi_constants.h) and the level kinds of fimex_amd_vertical_levels
+VINT_METHOD_LIN, VINT_METHOD_LOG, VINT_METHOD_LOGLOG, VINT_METHOD_NN = 0, 1, 2, 3
+VINT_METHOD_LIN_WEAK_EXTRA, VINT_METHOD_LIN_NO_EXTRA, VINT_METHOD_LIN_CONST_EXTRA = 4, 5, 6
+VLEVEL_FIELD, VLEVEL_AXIS, VLEVEL_SIGMA, VLEVEL_HYBRID_SIGMA, VLEVEL_HYBRID_SIGMA_AP = 0, 1, 2, 3, 4
+
+
+class VerticalLevelsStruct(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_int), ("nz", ctypes.c_size_t),
+                ("axis", ctypes.c_void_p), ("sigma", ctypes.c_void_p), ("a", ctypes.c_void_p), ("ap", ctypes.c_void_p),
+                ("b", ctypes.c_void_p), ("p0", ctypes.c_double), ("ptop", ctypes.c_double),
+                ("ps", ctypes.c_void_p), ("field", ctypes.c_void_p)]
+
+
 _F = ctypes.POINTER(ctypes.c_float)
 _D = ctypes.POINTER(ctypes.c_double)
 _Z = ctypes.c_size_t
@@ -109,6 +122,13 @@ SYMBOLS = {
     "fimex_amd_get_values_1d_f_device": (ctypes.c_int, [ctypes.c_int, _V, _V, _V, _Z, ctypes.c_double, ctypes.c_double, ctypes.c_double, _V]),
     "fimex_amd_get_values_1d_f_host": (ctypes.c_int, [ctypes.c_int, _F, _F, _F, _Z, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     "fimex_amd_get_values_linear_d_device": (ctypes.c_int, [_V, _V, _V, _Z, ctypes.c_double, ctypes.c_double, ctypes.c_double, _V]),
+    "fimex_amd_vertical_interpolate_device": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, _V, ctypes.POINTER(VerticalLevelsStruct),
+                                                             ctypes.POINTER(VerticalLevelsStruct), _D, _Z, _V, _V, ctypes.c_float, ctypes.c_float,
+                                                             _V, _V]),
+    "fimex_amd_vertical_interpolate_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, _F, ctypes.POINTER(VerticalLevelsStruct),
+                                                           ctypes.POINTER(VerticalLevelsStruct), _D, _Z, _D, _D, ctypes.c_float, ctypes.c_float, _F]),
+    "fimex_amd_vertical_levels_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V]),
+    "fimex_amd_vertical_levels_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F]),
     "fimex_amd_project_values_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z]),
     "fimex_amd_project_values_device": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _V, _V, _Z, _V]),
     "fimex_amd_project_axes_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z, _Z, _D, _D]),
@@ -505,6 +525,99 @@ def get_values_1d_device(kind, d_A, d_B, d_out, n, a, b, x, stream=0):
 
 def get_values_linear_d_device(d_A, d_B, d_out, n, a, b, x, stream=0):
     _check(load().fimex_amd_get_values_linear_d_device(d_A, d_B, d_out, n, a, b, x, stream))
+
+
+class VerticalLevels:
+    """fimex_amd_vertical_levels.  The coefficient arrays (axis, sigma, a, ap, b) are host arrays of nz doubles; ps ([nt][ny][nx]) and
+    field ([nt][nz][ny][nx]) are numpy float32 arrays for the *_host calls and device pointers (ints, e.g. tensor.data_ptr()) for
+    the *_device calls.  This object keeps the numpy arrays alive."""
+
+    def __init__(self, kind, nz, axis=None, sigma=None, a=None, ap=None, b=None, p0=0.0, ptop=0.0, ps=None, field=None):
+        self._keep = []
+        self.kind, self.nz = kind, nz
+        s = VerticalLevelsStruct()
+        s.kind, s.nz, s.p0, s.ptop = kind, nz, p0, ptop
+        for name, v in (("axis", axis), ("sigma", sigma), ("a", a), ("ap", ap), ("b", b)):
+            if v is not None:
+                arr = _f64(v).ravel()
+                if arr.size != nz:
+                    raise ValueError("%s must hold nz doubles" % name)
+                self._keep.append(arr)
+                setattr(s, name, arr.ctypes.data)
+        for name, v in (("ps", ps), ("field", field)):
+            if v is None:
+                continue
+            if isinstance(v, int):
+                setattr(s, name, v)
+            else:
+                arr = _f32(v)
+                self._keep.append(arr)
+                setattr(s, name, arr.ctypes.data)
+        self.struct = s
+
+    @classmethod
+    def from_field(cls, field, nz):
+        return cls(VLEVEL_FIELD, nz, field=field)
+
+    @classmethod
+    def from_axis(cls, axis):
+        return cls(VLEVEL_AXIS, len(axis), axis=axis)
+
+    @classmethod
+    def sigma(cls, sigma, ptop, ps):
+        return cls(VLEVEL_SIGMA, len(sigma), sigma=sigma, ptop=ptop, ps=ps)
+
+    @classmethod
+    def hybrid_sigma(cls, a, b, p0, ps):
+        return cls(VLEVEL_HYBRID_SIGMA, len(a), a=a, b=b, p0=p0, ps=ps)
+
+    @classmethod
+    def hybrid_sigma_ap(cls, ap, b, ps):
+        return cls(VLEVEL_HYBRID_SIGMA_AP, len(ap), ap=ap, b=b, ps=ps)
+
+
+def _levels_ref(levels):
+    return ctypes.byref(levels.struct) if levels is not None else None
+
+
+def vertical_interpolate_host(method, data, inLevels, outLevels=None, level1=None, validMin=None, validMax=None,
+                              clampMin=float("nan"), clampMax=float("nan")):
+    """CDMVerticalInterpolator::getLevelDataSlice on host arrays: data [nt][nzi][ny][nx] -> [nt][nzo][ny][nx], to the fixed levels
+    level1 or to the levels of the template description outLevels."""
+    d = _f32(data)
+    nt, nzi, ny, nx = d.shape
+    l1 = _f64(level1).ravel() if level1 is not None else None
+    nzo = outLevels.nz if outLevels is not None else (l1.size if l1 is not None else 0)
+    vmin = _f64(validMin) if validMin is not None else None
+    vmax = _f64(validMax) if validMax is not None else None
+    out = np.empty((nt, nzo, ny, nx), np.float32)
+    _check(load().fimex_amd_vertical_interpolate_host(method, nx, ny, nt, _fp(d.reshape(-1)), _levels_ref(inLevels), _levels_ref(outLevels),
+                                                      _dp(l1) if l1 is not None else None, nzo,
+                                                      _dp(vmin.reshape(-1)) if vmin is not None else None,
+                                                      _dp(vmax.reshape(-1)) if vmax is not None else None, clampMin, clampMax,
+                                                      _fp(out.reshape(-1))))
+    return out
+
+
+def vertical_interpolate_device(method, nx, ny, nt, d_in, inLevels, d_out, outLevels=None, level1=None, d_validMin=None, d_validMax=None,
+                                clampMin=float("nan"), clampMax=float("nan"), stream=0):
+    """The same on device pointers; only enqueues on `stream`.  level1 stays a host array."""
+    l1 = _f64(level1).ravel() if level1 is not None else None
+    nzo = outLevels.nz if outLevels is not None else (l1.size if l1 is not None else 0)
+    _check(load().fimex_amd_vertical_interpolate_device(method, nx, ny, nt, d_in, _levels_ref(inLevels), _levels_ref(outLevels),
+                                                        _dp(l1) if l1 is not None else None, nzo, d_validMin, d_validMax,
+                                                        clampMin, clampMax, d_out, stream))
+
+
+def vertical_levels_host(levels, nx, ny, nt):
+    """verticalData4D of a level description: float32 [nt][nz][ny][nx]."""
+    out = np.empty((nt, levels.nz, ny, nx), np.float32)
+    _check(load().fimex_amd_vertical_levels_host(_levels_ref(levels), nx, ny, nt, _fp(out.reshape(-1))))
+    return out
+
+
+def vertical_levels_device(levels, nx, ny, nt, d_out, stream=0):
+    _check(load().fimex_amd_vertical_levels_device(_levels_ref(levels), nx, ny, nt, d_out, stream))
 
 
 def project_values_host(proj_input, proj_output, x, y):

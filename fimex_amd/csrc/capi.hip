@@ -1081,3 +1081,126 @@ int fimex_amd_scan_sum_device(const float* d_values, size_t n, int mode, double 
 }
 
 }  // extern "C"
+
+// ---- vertical interpolation (8f n5)
+namespace {
+
+// everything fimex_amd_vertical_interpolate_* refuses before any work is queued; returns false when there is nothing to do
+bool check_vertical_call(int method, size_t nx, size_t ny, size_t nt, const void* in, const fimex_amd_vertical_levels* inLevels,
+                         const fimex_amd_vertical_levels* outLevels, const double* level1, size_t nzo, const void* out)
+{
+    using namespace fimex_amd;
+    FA_REQUIRE(vertical_method_known(method), "unknown vertical interpolation method " + std::to_string(method));
+    const bool nonEmpty = nx * ny * nt > 0;
+    check_vertical_levels(inLevels, "input", nonEmpty);
+    if (outLevels) {
+        check_vertical_levels(outLevels, "template", nonEmpty);
+        FA_REQUIRE(outLevels->nz == nzo, "nzo differs from the template's number of levels");
+    }
+    if (!nonEmpty) return false;
+    FA_REQUIRE(outLevels != nullptr || level1 != nullptr, "fixed levels need level1[nzo]");
+    FA_REQUIRE(inLevels->nz > 0, "no input levels (nzi == 0)");
+    FA_REQUIRE(nzo > 0, "no output levels (nzo == 0)");
+    FA_REQUIRE(in != nullptr && out != nullptr, "NULL data buffer");
+    const char *i0 = static_cast<const char*>(in), *o0 = static_cast<const char*>(out);
+    const size_t cells = nx * ny * nt * sizeof(float);
+    FA_REQUIRE(o0 + cells * nzo <= i0 || i0 + cells * inLevels->nz <= o0, "the output buffer overlaps the input buffer");
+    return true;
+}
+
+// device copies of the 2-D / 3-D members of a host-side level description
+struct HostLevels {
+    fimex_amd_vertical_levels d;
+    fimex_amd::DeviceArray<float> ps, field;
+    HostLevels(const fimex_amd_vertical_levels& h, size_t plane, size_t nt, hipStream_t stream) : d(h)
+    {
+        using namespace fimex_amd;
+        d.ps = nullptr;
+        d.field = nullptr;
+        if (h.kind == FIMEX_AMD_VLEVEL_FIELD) {
+            field.allocate(nt * h.nz * plane);
+            host_to_device(field.get(), h.field, field.bytes(), stream);
+            d.field = field.get();
+        } else if (h.kind != FIMEX_AMD_VLEVEL_AXIS) {
+            ps.allocate(nt * plane);
+            host_to_device(ps.get(), h.ps, ps.bytes(), stream);
+            d.ps = ps.get();
+        }
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+int fimex_amd_vertical_interpolate_device(int method, size_t nx, size_t ny, size_t nt, const float* d_in,
+                                          const fimex_amd_vertical_levels* inLevels, const fimex_amd_vertical_levels* outLevels,
+                                          const double* level1, size_t nzo, const double* d_validMin, const double* d_validMax,
+                                          float clampMin, float clampMax, float* d_out, void* stream)
+{
+    return c_guard([&] {
+        if (!check_vertical_call(method, nx, ny, nt, d_in, inLevels, outLevels, level1, nzo, d_out)) return;
+        (void)current_device_checked();
+        launch_vertical_interpolate(method, nx, ny, nt, d_in, *inLevels, outLevels, level1, nzo, d_validMin, d_validMax, clampMin, clampMax,
+                                    d_out, as_stream(stream));
+    });
+}
+
+int fimex_amd_vertical_interpolate_host(int method, size_t nx, size_t ny, size_t nt, const float* in,
+                                        const fimex_amd_vertical_levels* inLevels, const fimex_amd_vertical_levels* outLevels,
+                                        const double* level1, size_t nzo, const double* validMin, const double* validMax,
+                                        float clampMin, float clampMax, float* out)
+{
+    return c_guard([&] {
+        if (!check_vertical_call(method, nx, ny, nt, in, inLevels, outLevels, level1, nzo, out)) return;
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t plane = nx * ny;
+        DeviceArray<float> d_in(nt * inLevels->nz * plane), d_out(nt * nzo * plane);
+        DeviceArray<double> d_valid((validMin ? plane : 0) + (validMax ? plane : 0));
+        double* d_min = validMin ? d_valid.get() : nullptr;
+        double* d_max = validMax ? d_valid.get() + (validMin ? plane : 0) : nullptr;
+        host_to_device(d_in.get(), in, d_in.bytes(), stream.get());
+        if (d_min) host_to_device(d_min, validMin, plane * sizeof(double), stream.get());
+        if (d_max) host_to_device(d_max, validMax, plane * sizeof(double), stream.get());
+        HostLevels li(*inLevels, plane, nt, stream.get());
+        std::unique_ptr<HostLevels> lo;
+        if (outLevels) lo = std::make_unique<HostLevels>(*outLevels, plane, nt, stream.get());
+        launch_vertical_interpolate(method, nx, ny, nt, d_in.get(), li.d, lo ? &lo->d : nullptr, level1, nzo, d_min, d_max, clampMin, clampMax,
+                                    d_out.get(), stream.get());
+        device_to_host(out, d_out.get(), d_out.bytes(), stream.get());
+        stream.sync();
+    });
+}
+
+int fimex_amd_vertical_levels_device(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* d_out, void* stream)
+{
+    return c_guard([&] {
+        const bool nonEmpty = nx * ny * nt > 0;
+        check_vertical_levels(levels, "the", nonEmpty);
+        if (!nonEmpty || levels->nz == 0) return;
+        FA_REQUIRE(d_out != nullptr, "NULL device buffer");
+        (void)current_device_checked();
+        launch_vertical_levels(*levels, nx, ny, nt, d_out, as_stream(stream));
+    });
+}
+
+int fimex_amd_vertical_levels_host(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* out)
+{
+    return c_guard([&] {
+        const bool nonEmpty = nx * ny * nt > 0;
+        check_vertical_levels(levels, "the", nonEmpty);
+        if (!nonEmpty || levels->nz == 0) return;
+        FA_REQUIRE(out != nullptr, "NULL argument");
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t plane = nx * ny;
+        HostLevels l(*levels, plane, nt, stream.get());
+        DeviceArray<float> d_out(nt * levels->nz * plane);
+        launch_vertical_levels(l.d, nx, ny, nt, d_out.get(), stream.get());
+        device_to_host(out, d_out.get(), d_out.bytes(), stream.get());
+        stream.sync();
+    });
+}
+
+}  // extern "C"

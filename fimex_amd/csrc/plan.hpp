@@ -185,6 +185,14 @@ void launch_interpolation2data(const float* d_in, size_t n, int cdmType, double 
 bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                         hipStream_t stream);
 
+// vertical.hip: vertical interpolation to fixed or template levels
+bool vertical_method_known(int method);
+void check_vertical_levels(const fimex_amd_vertical_levels* levels, const char* which, bool nonEmpty);  // throws: unknown kind, missing array
+void launch_vertical_interpolate(int method, size_t nx, size_t ny, size_t nt, const float* d_in, const fimex_amd_vertical_levels& inLevels,
+                                 const fimex_amd_vertical_levels* outLevels, const double* h_level1, size_t nzo, const double* d_validMin,
+                                 const double* d_validMax, float clampMin, float clampMax, float* d_out, hipStream_t stream);
+void launch_vertical_levels(const fimex_amd_vertical_levels& levels, size_t nx, size_t ny, size_t nt, float* d_out, hipStream_t stream);
+
 // projection.hip: pj_transform-level plan building on the device
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);
 void launch_project_axes(const char* projIn, const char* projOut, const double* h_xAxis, const double* h_yAxis, size_t ix, size_t iy,

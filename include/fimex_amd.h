@@ -367,6 +367,70 @@ int fimex_amd_get_values_1d_f_host(int kind, const float* infieldA, const float*
 int fimex_amd_get_values_linear_d_device(const double* d_infieldA, const double* d_infieldB, double* d_outfield, size_t n,
                                          double a, double b, double x, void* stream);
 
+/* ------------------------------------------------ vertical interpolation (8f n5) */
+/** Values of enum mifi_vertical_interpol_method, include/fimex/mifi_constants.h:202-231. */
+#define FIMEX_AMD_VINT_METHOD_LIN 0
+#define FIMEX_AMD_VINT_METHOD_LOG 1
+#define FIMEX_AMD_VINT_METHOD_LOGLOG 2
+#define FIMEX_AMD_VINT_METHOD_NN 3
+#define FIMEX_AMD_VINT_METHOD_LIN_WEAK_EXTRA 4
+#define FIMEX_AMD_VINT_METHOD_LIN_NO_EXTRA 5
+#define FIMEX_AMD_VINT_METHOD_LIN_CONST_EXTRA 6
+
+/** How the levels of a column are given: what the reference's VerticalConverter would put into verticalData4D. */
+#define FIMEX_AMD_VLEVEL_FIELD 0            /* explicit f32 field [nt][nz][ny][nx] */
+#define FIMEX_AMD_VLEVEL_AXIS 1             /* axis[nz], the same in every column (pressure / height axis, IdentityConverter) */
+#define FIMEX_AMD_VLEVEL_SIGMA 2            /* ptop + sigma[k] * (ps - ptop), src/vertical_coordinate_transformations.c:37-44 */
+#define FIMEX_AMD_VLEVEL_HYBRID_SIGMA 3     /* a[k] * p0 + b[k] * ps, :57-63 */
+#define FIMEX_AMD_VLEVEL_HYBRID_SIGMA_AP 4  /* ap[k] + b[k] * ps, :65-71 */
+
+/**
+ * The levels of every column of a [nt][nz][ny][nx] variable.  Formula kinds are evaluated in double in the reference's
+ * operation order and rounded to float (Data::asFloat()); nothing 3-D exists in memory for them.
+ * axis, sigma, a, ap, b: HOST arrays of nz doubles in the *_device and the *_host entry points alike; they are copied by
+ * the call.  ps ([nt][ny][nx], already in the unit of the coefficients) and field follow the entry point: device pointers
+ * for *_device, host pointers for *_host.  Members a kind does not use are ignored.
+ */
+typedef struct fimex_amd_vertical_levels {
+    int kind;             /* FIMEX_AMD_VLEVEL_* */
+    size_t nz;
+    const double* axis;   /* AXIS */
+    const double* sigma;  /* SIGMA */
+    const double* a;      /* HYBRID_SIGMA */
+    const double* ap;     /* HYBRID_SIGMA_AP */
+    const double* b;      /* HYBRID_SIGMA, HYBRID_SIGMA_AP */
+    double p0;            /* HYBRID_SIGMA */
+    double ptop;          /* SIGMA */
+    const float* ps;      /* SIGMA, HYBRID_SIGMA, HYBRID_SIGMA_AP */
+    const float* field;   /* FIELD */
+} fimex_amd_vertical_levels;
+
+/**
+ * Replaces the loop of CDMVerticalInterpolator::getLevelDataSlice (src/CDMVerticalInterpolator.cc:441-504) for a batch of nt
+ * unlimited-dimension positions: d_in [nt][inLevels->nz][ny][nx] -> d_out [nt][nzo][ny][nx].  Per column and output level:
+ * the target level x is level1[k] (outLevels == NULL: fixed levels, host double[nzo]) or the level outLevels describes
+ * (interpolateByTemplateVariable; nzo must equal outLevels->nz, level1 is ignored); x outside [validMin, validMax] of the
+ * column (double[ny][nx] each, NULL: no bound) gives NaN (:454-471); the bracketing input levels are those of
+ * find_closest_neighbor_distinct_elements (include/fimex/Utils.h:204-290) run over the column in index order; the two data
+ * values are blended by mifi_get_values_*_f with n = 1 (src/interpolation.c:1030-1156); the result is clamped to
+ * [clampMin, clampMax] (NaN: no bound; :494-504).
+ * One divergence: where the log blends return MIFI_ERROR (a non-positive level) the reference leaves the output element
+ * uninitialised; NaN is written here.
+ * Only enqueues work on the stream and never synchronises it.  d_out must not overlap d_in.
+ */
+int fimex_amd_vertical_interpolate_device(int method, size_t nx, size_t ny, size_t nt, const float* d_in,
+                                          const fimex_amd_vertical_levels* inLevels, const fimex_amd_vertical_levels* outLevels,
+                                          const double* level1, size_t nzo, const double* d_validMin, const double* d_validMax,
+                                          float clampMin, float clampMax, float* d_out, void* stream);
+/** The same on host buffers (in, inLevels->ps / ->field, outLevels->ps / ->field, validMin, validMax, out). */
+int fimex_amd_vertical_interpolate_host(int method, size_t nx, size_t ny, size_t nt, const float* in,
+                                        const fimex_amd_vertical_levels* inLevels, const fimex_amd_vertical_levels* outLevels,
+                                        const double* level1, size_t nzo, const double* validMin, const double* validMax,
+                                        float clampMin, float clampMax, float* out);
+/** What verticalData4D returns for a level description: the f32 field [nt][levels->nz][ny][nx]. */
+int fimex_amd_vertical_levels_device(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* d_out, void* stream);
+int fimex_amd_vertical_levels_host(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* out);
+
 /* ----------------------------------- plan building across projections (8f n2) */
 /* The reference calls PROJ.4 (pj_init_plus / pj_transform) here; this library carries its own projections:
  * latlong/longlat, stere, lcc, merc, tmerc, etmerc, utm, laea, aea, geos, omerc, sinu, cea, ortho, aeqd, nsper, ob_tran with o_proj=longlat (radians at this boundary for
