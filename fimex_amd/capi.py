@@ -57,6 +57,8 @@ PROCESS_FILL2D, PROCESS_CREEPFILL2D, PROCESS_CREEPFILLVAL2D = 1, 2, 3
 VINT_METHOD_LIN, VINT_METHOD_LOG, VINT_METHOD_LOGLOG, VINT_METHOD_NN = 0, 1, 2, 3
 VINT_METHOD_LIN_WEAK_EXTRA, VINT_METHOD_LIN_NO_EXTRA, VINT_METHOD_LIN_CONST_EXTRA = 4, 5, 6
 VLEVEL_FIELD, VLEVEL_AXIS, VLEVEL_SIGMA, VLEVEL_HYBRID_SIGMA, VLEVEL_HYBRID_SIGMA_AP = 0, 1, 2, 3, 4
+# surfaceFirst of fimex_amd_vertical_altitude_integrate_*
+VORDER_AUTO, VORDER_SURFACE_LAST, VORDER_SURFACE_FIRST = -1, 0, 1
 
 
 class VerticalLevelsStruct(ctypes.Structure):
@@ -129,6 +131,16 @@ SYMBOLS = {
                                                            ctypes.POINTER(VerticalLevelsStruct), _D, _Z, _D, _D, ctypes.c_float, ctypes.c_float, _F]),
     "fimex_amd_vertical_levels_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V]),
     "fimex_amd_vertical_levels_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F]),
+    "fimex_amd_vertical_altitude_integrate_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V, _V, _V, ctypes.c_int,
+                                                                    _V, ctypes.c_double, _V, _V]),
+    "fimex_amd_vertical_altitude_integrate_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F, _F, _F, _F, ctypes.c_int,
+                                                                  _D, ctypes.c_double, _F]),
+    "fimex_amd_vertical_standard_altitude_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, ctypes.c_double, _V, _V]),
+    "fimex_amd_vertical_standard_altitude_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _D, ctypes.c_double, _F]),
+    "fimex_amd_vertical_standard_pressure_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, ctypes.c_double, _V, _V]),
+    "fimex_amd_vertical_standard_pressure_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _D, ctypes.c_double, _F]),
+    "fimex_amd_vertical_ocean_depth_device": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, _Z, _D, _D, ctypes.c_double, _V, _V, _V, _V]),
+    "fimex_amd_vertical_ocean_depth_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, _Z, _D, _D, ctypes.c_double, _D, _D, _F]),
     "fimex_amd_project_values_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z]),
     "fimex_amd_project_values_device": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _V, _V, _Z, _V]),
     "fimex_amd_project_axes_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z, _Z, _D, _D]),
@@ -618,6 +630,82 @@ def vertical_levels_host(levels, nx, ny, nt):
 
 def vertical_levels_device(levels, nx, ny, nt, d_out, stream=0):
     _check(load().fimex_amd_vertical_levels_device(_levels_ref(levels), nx, ny, nt, d_out, stream))
+
+
+def _opt(conv, ptr, v):
+    """A host array as a pointer (None stays NULL); returns (array kept alive, pointer)."""
+    if v is None:
+        return None, None
+    arr = conv(v)
+    return arr, ptr(arr.reshape(-1))
+
+
+def vertical_altitude_integrate_host(pressure, nx, ny, nt, airTemperature, surfacePressure, surfaceGeopotential, specificHumidity=None,
+                                     surfaceFirst=VORDER_AUTO, topo=None, topoFactor=-1.0):
+    """PressureIntegrationToAltitudeConverter (then AltitudeHeightConverter when topo is given) on host arrays:
+    float32 [nt][nz][ny][nx]."""
+    T, Tp = _opt(_f32, _fp, airTemperature)
+    q, qp = _opt(_f32, _fp, specificHumidity)
+    sap, sapp = _opt(_f32, _fp, surfacePressure)
+    sgp, sgpp = _opt(_f32, _fp, surfaceGeopotential)
+    tp, tpp = _opt(_f64, _dp, topo)
+    out = np.empty((nt, pressure.nz, ny, nx), np.float32)
+    _check(load().fimex_amd_vertical_altitude_integrate_host(_levels_ref(pressure), nx, ny, nt, Tp, qp, sapp, sgpp, surfaceFirst, tpp, topoFactor,
+                                                             _fp(out.reshape(-1))))
+    return out
+
+
+def vertical_altitude_integrate_device(pressure, nx, ny, nt, d_airTemperature, d_surfacePressure, d_surfaceGeopotential, d_out,
+                                       d_specificHumidity=None, surfaceFirst=VORDER_AUTO, d_topo=None, topoFactor=-1.0, stream=0):
+    """The same on device pointers; only enqueues on `stream`."""
+    _check(load().fimex_amd_vertical_altitude_integrate_device(_levels_ref(pressure), nx, ny, nt, d_airTemperature, d_specificHumidity,
+                                                               d_surfacePressure, d_surfaceGeopotential, surfaceFirst, d_topo, topoFactor,
+                                                               d_out, stream))
+
+
+def _standard_host(fn, levels, nx, ny, nt, topo, topoFactor):
+    tp, tpp = _opt(_f64, _dp, topo)
+    out = np.empty((nt, levels.nz, ny, nx), np.float32)
+    _check(fn(_levels_ref(levels), nx, ny, nt, tpp, topoFactor, _fp(out.reshape(-1))))
+    return out
+
+
+def vertical_standard_altitude_host(pressure, nx, ny, nt, topo=None, topoFactor=-1.0):
+    """PressureToStandardAltitudeConverter (+ AltitudeHeightConverter with topo): float32 [nt][nz][ny][nx]."""
+    return _standard_host(load().fimex_amd_vertical_standard_altitude_host, pressure, nx, ny, nt, topo, topoFactor)
+
+
+def vertical_standard_altitude_device(pressure, nx, ny, nt, d_out, d_topo=None, topoFactor=-1.0, stream=0):
+    _check(load().fimex_amd_vertical_standard_altitude_device(_levels_ref(pressure), nx, ny, nt, d_topo, topoFactor, d_out, stream))
+
+
+def vertical_standard_pressure_host(altitude, nx, ny, nt, topo=None, topoFactor=1.0):
+    """AltitudeStandardToPressureConverter (behind an AltitudeHeightConverter with topo): float32 [nt][nz][ny][nx]."""
+    return _standard_host(load().fimex_amd_vertical_standard_pressure_host, altitude, nx, ny, nt, topo, topoFactor)
+
+
+def vertical_standard_pressure_device(altitude, nx, ny, nt, d_out, d_topo=None, topoFactor=1.0, stream=0):
+    _check(load().fimex_amd_vertical_standard_pressure_device(_levels_ref(altitude), nx, ny, nt, d_topo, topoFactor, d_out, stream))
+
+
+def vertical_ocean_depth_host(generation, nx, ny, nt, s, C, depth_c, depth, eta=None):
+    """OceanSCoordinateGToDepthConverter: float32 [nt][nz][ny][nx], positive down."""
+    sa, sp = _opt(_f64, _dp, s)
+    ca, cp = _opt(_f64, _dp, C)
+    da, dpp = _opt(_f64, _dp, depth)
+    ea, ep = _opt(_f64, _dp, eta)
+    nz = sa.size if sa is not None else 0
+    out = np.empty((nt, nz, ny, nx), np.float32)
+    _check(load().fimex_amd_vertical_ocean_depth_host(generation, nx, ny, nz, nt, sp, cp, depth_c, dpp, ep, _fp(out.reshape(-1))))
+    return out
+
+
+def vertical_ocean_depth_device(generation, nx, ny, nt, s, C, depth_c, d_depth, d_out, d_eta=None, stream=0):
+    """s and C stay host arrays."""
+    sa, sp = _opt(_f64, _dp, s)
+    ca, cp = _opt(_f64, _dp, C)
+    nz = sa.size if sa is not None else 0
+    _check(load().fimex_amd_vertical_ocean_depth_device(generation, nx, ny, nz, nt, sp, cp, depth_c, d_depth, d_eta, d_out, stream))
 
 
 def project_values_host(proj_input, proj_output, x, y):

@@ -6,6 +6,8 @@
 #include <memory>
 #include <algorithm>
 #include <vector>
+#include <initializer_list>
+#include <string>
 
 namespace fimex_amd {
 
@@ -1198,6 +1200,224 @@ int fimex_amd_vertical_levels_host(const fimex_amd_vertical_levels* levels, size
         HostLevels l(*levels, plane, nt, stream.get());
         DeviceArray<float> d_out(nt * levels->nz * plane);
         launch_vertical_levels(l.d, nx, ny, nt, d_out.get(), stream.get());
+        device_to_host(out, d_out.get(), d_out.bytes(), stream.get());
+        stream.sync();
+    });
+}
+
+}  // extern "C"
+
+// ---- vertical level converters (8f n6)
+namespace {
+
+struct Span {
+    const void* p;
+    size_t bytes;
+    const char* name;
+};
+
+// the output buffer against every buffer the call reads
+void require_no_overlap(const void* out, size_t outBytes, std::initializer_list<Span> inputs)
+{
+    const char* o0 = static_cast<const char*>(out);
+    for (const Span& s : inputs) {
+        if (!s.p || !s.bytes) continue;
+        const char* i0 = static_cast<const char*>(s.p);
+        FA_REQUIRE(o0 + outBytes <= i0 || i0 + s.bytes <= o0, std::string("the output buffer overlaps ") + s.name);
+    }
+}
+
+// the 2-D / 3-D members of a level description as inputs of require_no_overlap
+void require_no_overlap_with_levels(const void* out, size_t outBytes, const fimex_amd_vertical_levels& l, size_t cells)
+{
+    const bool field = l.kind == FIMEX_AMD_VLEVEL_FIELD, ps = !field && l.kind != FIMEX_AMD_VLEVEL_AXIS;
+    require_no_overlap(out, outBytes, {{field ? l.field : nullptr, cells * l.nz * sizeof(float), "the level field"},
+                                       {ps ? l.ps : nullptr, cells * sizeof(float), "ps"}});
+}
+
+// false: nothing to do
+bool check_altitude_call(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* T, const float* q,
+                         const float* sap, const float* sgp, int surfaceFirst, const double* topo, const float* out)
+{
+    using namespace fimex_amd;
+    FA_REQUIRE(vertical_order_known(surfaceFirst), "unknown surfaceFirst " + std::to_string(surfaceFirst) + " (1, 0 or -1 for the reference's rule)");
+    const bool nonEmpty = nx * ny * nt > 0;
+    check_vertical_levels(pressure, "pressure", nonEmpty);
+    if (!nonEmpty) return false;
+    FA_REQUIRE(pressure->nz > 0, "no levels (nz == 0)");
+    FA_REQUIRE(T != nullptr, "NULL air temperature");
+    FA_REQUIRE(sap != nullptr, "NULL surface pressure");
+    FA_REQUIRE(sgp != nullptr, "NULL surface geopotential");
+    FA_REQUIRE(out != nullptr, "NULL output buffer");
+    const size_t cells = nx * ny * nt, vol = cells * pressure->nz * sizeof(float);
+    require_no_overlap(out, vol, {{T, vol, "the air temperature"}, {q, vol, "the specific humidity"},
+                                  {sap, cells * sizeof(float), "the surface pressure"}, {sgp, cells * sizeof(float), "the surface geopotential"},
+                                  {topo, nx * ny * sizeof(double), "the topography"}});
+    require_no_overlap_with_levels(out, vol, *pressure, cells);
+    return true;
+}
+
+bool check_standard_call(const fimex_amd_vertical_levels* levels, const char* which, size_t nx, size_t ny, size_t nt, const double* topo,
+                         const float* out)
+{
+    using namespace fimex_amd;
+    const bool nonEmpty = nx * ny * nt > 0;
+    check_vertical_levels(levels, which, nonEmpty);
+    if (!nonEmpty) return false;
+    FA_REQUIRE(levels->nz > 0, "no levels (nz == 0)");
+    FA_REQUIRE(out != nullptr, "NULL output buffer");
+    const size_t cells = nx * ny * nt, vol = cells * levels->nz * sizeof(float);
+    require_no_overlap(out, vol, {{topo, nx * ny * sizeof(double), "the topography"}});
+    require_no_overlap_with_levels(out, vol, *levels, cells);
+    return true;
+}
+
+bool check_ocean_call(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* s, const double* C, const double* depth,
+                      const double* eta, const float* out)
+{
+    FA_REQUIRE(generation == 1 || generation == 2, "unknown ocean s-coordinate generation " + std::to_string(generation) + " (1 or 2)");
+    FA_REQUIRE(nz <= 0x7fffffffu, "nz out of range");
+    if (nx * ny * nt == 0) return false;
+    FA_REQUIRE(nz > 0, "no levels (nz == 0)");
+    FA_REQUIRE(s != nullptr && C != nullptr, "NULL s[nz] or C[nz]");
+    FA_REQUIRE(depth != nullptr, "NULL depth");
+    FA_REQUIRE(out != nullptr, "NULL output buffer");
+    require_no_overlap(out, nx * ny * nt * nz * sizeof(float), {{depth, nx * ny * sizeof(double), "the depth"},
+                                                                {eta, nx * ny * nt * sizeof(double), "eta"}});
+    return true;
+}
+
+// a host array on the device, or nothing for NULL
+template <class T>
+T* to_device(fimex_amd::DeviceArray<T>& d, const T* h, size_t n, hipStream_t stream)
+{
+    if (!h) return nullptr;
+    d.allocate(n);
+    fimex_amd::host_to_device(d.get(), h, d.bytes(), stream);
+    return d.get();
+}
+
+int standard_device(bool toPressure, const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, const double* d_topo,
+                    double topoFactor, float* d_out, void* stream)
+{
+    using namespace fimex_amd;
+    return c_guard([&] {
+        if (!check_standard_call(levels, toPressure ? "altitude" : "pressure", nx, ny, nt, d_topo, d_out)) return;
+        (void)current_device_checked();
+        launch_vertical_standard(toPressure, *levels, nx, ny, nt, d_topo, topoFactor, d_out, as_stream(stream));
+    });
+}
+
+int standard_host(bool toPressure, const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, const double* topo,
+                  double topoFactor, float* out)
+{
+    using namespace fimex_amd;
+    return c_guard([&] {
+        if (!check_standard_call(levels, toPressure ? "altitude" : "pressure", nx, ny, nt, topo, out)) return;
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t plane = nx * ny;
+        HostLevels l(*levels, plane, nt, stream.get());
+        DeviceArray<double> d_topo;
+        DeviceArray<float> d_out(nt * levels->nz * plane);
+        launch_vertical_standard(toPressure, l.d, nx, ny, nt, to_device(d_topo, topo, plane, stream.get()), topoFactor, d_out.get(), stream.get());
+        device_to_host(out, d_out.get(), d_out.bytes(), stream.get());
+        stream.sync();
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int fimex_amd_vertical_altitude_integrate_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt,
+                                                 const float* d_airTemperature, const float* d_specificHumidity,
+                                                 const float* d_surfacePressure, const float* d_surfaceGeopotential, int surfaceFirst,
+                                                 const double* d_topo, double topoFactor, float* d_out, void* stream)
+{
+    return c_guard([&] {
+        if (!check_altitude_call(pressure, nx, ny, nt, d_airTemperature, d_specificHumidity, d_surfacePressure, d_surfaceGeopotential,
+                                 surfaceFirst, d_topo, d_out))
+            return;
+        (void)current_device_checked();
+        launch_vertical_altitude(*pressure, nx, ny, nt, d_airTemperature, d_specificHumidity, d_surfacePressure, d_surfaceGeopotential,
+                                 surfaceFirst, d_topo, topoFactor, d_out, as_stream(stream));
+    });
+}
+
+int fimex_amd_vertical_altitude_integrate_host(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt,
+                                               const float* airTemperature, const float* specificHumidity, const float* surfacePressure,
+                                               const float* surfaceGeopotential, int surfaceFirst, const double* topo, double topoFactor,
+                                               float* out)
+{
+    return c_guard([&] {
+        if (!check_altitude_call(pressure, nx, ny, nt, airTemperature, specificHumidity, surfacePressure, surfaceGeopotential, surfaceFirst,
+                                 topo, out))
+            return;
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t plane = nx * ny, vol = nt * pressure->nz * plane;
+        HostLevels l(*pressure, plane, nt, stream.get());
+        DeviceArray<float> d_T, d_q, d_sap, d_sgp, d_out(vol);
+        DeviceArray<double> d_topo;
+        const float* T = to_device(d_T, airTemperature, vol, stream.get());
+        const float* q = to_device(d_q, specificHumidity, vol, stream.get());
+        const float* sap = to_device(d_sap, surfacePressure, nt * plane, stream.get());
+        const float* sgp = to_device(d_sgp, surfaceGeopotential, nt * plane, stream.get());
+        launch_vertical_altitude(l.d, nx, ny, nt, T, q, sap, sgp, surfaceFirst, to_device(d_topo, topo, plane, stream.get()), topoFactor,
+                                 d_out.get(), stream.get());
+        device_to_host(out, d_out.get(), d_out.bytes(), stream.get());
+        stream.sync();
+    });
+}
+
+int fimex_amd_vertical_standard_altitude_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt,
+                                                const double* d_topo, double topoFactor, float* d_out, void* stream)
+{
+    return standard_device(false, pressure, nx, ny, nt, d_topo, topoFactor, d_out, stream);
+}
+
+int fimex_amd_vertical_standard_altitude_host(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const double* topo,
+                                              double topoFactor, float* out)
+{
+    return standard_host(false, pressure, nx, ny, nt, topo, topoFactor, out);
+}
+
+int fimex_amd_vertical_standard_pressure_device(const fimex_amd_vertical_levels* altitude, size_t nx, size_t ny, size_t nt,
+                                                const double* d_topo, double topoFactor, float* d_out, void* stream)
+{
+    return standard_device(true, altitude, nx, ny, nt, d_topo, topoFactor, d_out, stream);
+}
+
+int fimex_amd_vertical_standard_pressure_host(const fimex_amd_vertical_levels* altitude, size_t nx, size_t ny, size_t nt, const double* topo,
+                                              double topoFactor, float* out)
+{
+    return standard_host(true, altitude, nx, ny, nt, topo, topoFactor, out);
+}
+
+int fimex_amd_vertical_ocean_depth_device(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* s, const double* C,
+                                          double depth_c, const double* d_depth, const double* d_eta, float* d_out, void* stream)
+{
+    return c_guard([&] {
+        if (!check_ocean_call(generation, nx, ny, nz, nt, s, C, d_depth, d_eta, d_out)) return;
+        (void)current_device_checked();
+        launch_vertical_ocean_depth(generation, nx, ny, nz, nt, s, C, depth_c, d_depth, d_eta, d_out, as_stream(stream));
+    });
+}
+
+int fimex_amd_vertical_ocean_depth_host(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* s, const double* C,
+                                        double depth_c, const double* depth, const double* eta, float* out)
+{
+    return c_guard([&] {
+        if (!check_ocean_call(generation, nx, ny, nz, nt, s, C, depth, eta, out)) return;
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t plane = nx * ny;
+        DeviceArray<double> d_depth, d_eta;
+        DeviceArray<float> d_out(nt * nz * plane);
+        const double* dd = to_device(d_depth, depth, plane, stream.get());
+        launch_vertical_ocean_depth(generation, nx, ny, nz, nt, s, C, depth_c, dd, to_device(d_eta, eta, nt * plane, stream.get()), d_out.get(),
+                                    stream.get());
         device_to_host(out, d_out.get(), d_out.bytes(), stream.get());
         stream.sync();
     });

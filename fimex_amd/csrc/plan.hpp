@@ -193,6 +193,16 @@ void launch_vertical_interpolate(int method, size_t nx, size_t ny, size_t nt, co
                                  const double* d_validMax, float clampMin, float clampMax, float* d_out, hipStream_t stream);
 void launch_vertical_levels(const fimex_amd_vertical_levels& levels, size_t nx, size_t ny, size_t nt, float* d_out, hipStream_t stream);
 
+// vertical_levels.hip: the level converters for altitude, height and ocean depth
+bool vertical_order_known(int surfaceFirst);
+void launch_vertical_altitude(const fimex_amd_vertical_levels& pressure, size_t nx, size_t ny, size_t nt, const float* d_T, const float* d_q,
+                              const float* d_sap, const float* d_sgp, int surfaceFirst, const double* d_topo, double topoFactor, float* d_out,
+                              hipStream_t stream);
+void launch_vertical_standard(bool toPressure, const fimex_amd_vertical_levels& levels, size_t nx, size_t ny, size_t nt, const double* d_topo,
+                              double topoFactor, float* d_out, hipStream_t stream);
+void launch_vertical_ocean_depth(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* h_s, const double* h_C, double depth_c,
+                                 const double* d_depth, const double* d_eta, float* d_out, hipStream_t stream);
+
 // projection.hip: pj_transform-level plan building on the device
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);
 void launch_project_axes(const char* projIn, const char* projOut, const double* h_xAxis, const double* h_yAxis, size_t ix, size_t iy,

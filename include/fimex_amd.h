@@ -431,6 +431,76 @@ int fimex_amd_vertical_interpolate_host(int method, size_t nx, size_t ny, size_t
 int fimex_amd_vertical_levels_device(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* d_out, void* stream);
 int fimex_amd_vertical_levels_host(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* out);
 
+/* ------------------------ vertical level converters: altitude, height, depth (8f n6) */
+/* What the reference's VerticalConverter chain (src/coordSys/verticalTransform/) puts into verticalData4D for the vertical
+ * types MIFI_VINT_ALTITUDE, MIFI_VINT_HEIGHT and MIFI_VINT_DEPTH: an f32 field [nt][nz][ny][nx], which
+ * fimex_amd_vertical_interpolate_* take as FIMEX_AMD_VLEVEL_FIELD.  Whole columns only.  The *_device entries only enqueue
+ * work on the stream and never synchronise it; the *_host entries take host buffers for everything.  The coefficient arrays
+ * of a level description, s and C are host arrays in both.  The output must not overlap any input. */
+
+/** Which end of the vertical axis is next to the surface (surfaceFirst). */
+#define FIMEX_AMD_VORDER_AUTO (-1)  /* decided as the reference does, see below */
+#define FIMEX_AMD_VORDER_SURFACE_LAST 0
+#define FIMEX_AMD_VORDER_SURFACE_FIRST 1
+
+/**
+ * PressureIntegrationToAltitudeConverter::getDataSlice (PressureIntegrationToAltitudeConverter.cc:85-210): the altitude of
+ * every level by the hypsometric equation, integrated from the surface upward.  Per column: a = (double)sgp / 9.80665,
+ * p_low = sap; per level, p_high = the level's pressure as float, Tv = T or mifi_virtual_temperature(q, T) (q != NULL),
+ * a += (double)mifi_barometric_layer_thickness(p_low, p_high, Tv), p_low = p_high
+ * (src/vertical_coordinate_transformations.c:108-111, :154-157).  A NaN makes the column NaN from that level upward.
+ * pressure: the levels' pressure in the unit of surfacePressure (hPa in the reference); airTemperature and specificHumidity
+ * [nt][nz][ny][nx]; surfacePressure and surfaceGeopotential (m^2/s^2) [nt][ny][nx].
+ * surfaceFirst: 1 when level index 0 is next to the surface, 0 when the last index is, FIMEX_AMD_VORDER_AUTO to decide as the
+ * reference does (:105-122): index 0 is at the surface when the first level's pressure is greater than the last level's (both
+ * as float) in column x = 0, y = 0 of the batch's FIRST time step.  The reference looks at the file's first time step: a
+ * caller whose batch does not start there passes 0 or 1 to match it.
+ * topo == NULL: the result is (float)a.  Otherwise AltitudeHeightConverter::getDataSlice (AltitudeHeightConverter.cc:87-105)
+ * follows on the unrounded a: (float)(a + topoFactor * topo), topo double[ny][nx], topoFactor -1 (altitude to height) or +1,
+ * divided by 9.80665 when topo is a geopotential (:62-77).
+ */
+int fimex_amd_vertical_altitude_integrate_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt,
+                                                 const float* d_airTemperature, const float* d_specificHumidity,
+                                                 const float* d_surfacePressure, const float* d_surfaceGeopotential, int surfaceFirst,
+                                                 const double* d_topo, double topoFactor, float* d_out, void* stream);
+int fimex_amd_vertical_altitude_integrate_host(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt,
+                                               const float* airTemperature, const float* specificHumidity,
+                                               const float* surfacePressure, const float* surfaceGeopotential, int surfaceFirst,
+                                               const double* topo, double topoFactor, float* out);
+
+/**
+ * PressureToStandardAltitudeConverter::getDataSlice (:33-41): (-BAROMETRIC_FACTOR * 288.15) * log(p / 1013.25) in double
+ * (mifi_barometric_standard_altitude, src/vertical_coordinate_transformations.c:94-106), p in hPa.  The converter reads its
+ * inner converter's DOUBLE data: a formula kind enters unrounded, a FIELD as its floats promoted, an AXIS as its doubles.
+ * topo != NULL: (float)(altitude + topoFactor * topo) as above, otherwise (float)altitude.
+ */
+int fimex_amd_vertical_standard_altitude_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt,
+                                                const double* d_topo, double topoFactor, float* d_out, void* stream);
+int fimex_amd_vertical_standard_altitude_host(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt,
+                                              const double* topo, double topoFactor, float* out);
+
+/**
+ * AltitudeStandardToPressureConverter::getDataSlice (:33-41): 1013.25 * exp((-1 / (BAROMETRIC_FACTOR * 288.15)) * h) in double
+ * (mifi_barometric_standard_pressure, :79-91), hPa.  altitude: the levels in m, read as doubles as above.  topo != NULL: the
+ * levels are heights and an AltitudeHeightConverter stands in front, h = level + topoFactor * topo (topoFactor +1, or
+ * 1 / 9.80665 for a geopotential).
+ */
+int fimex_amd_vertical_standard_pressure_device(const fimex_amd_vertical_levels* altitude, size_t nx, size_t ny, size_t nt,
+                                                const double* d_topo, double topoFactor, float* d_out, void* stream);
+int fimex_amd_vertical_standard_pressure_host(const fimex_amd_vertical_levels* altitude, size_t nx, size_t ny, size_t nt,
+                                              const double* topo, double topoFactor, float* out);
+
+/**
+ * OceanSCoordinateGToDepthConverter::getDataSlice (:66-107): depth, positive down, of ocean_s_coordinate_g1 / _g2 levels:
+ * (float)(-z) with z of mifi_ocean_s_g1_z (generation 1) or mifi_ocean_s_g2_z (generation 2)
+ * (src/vertical_coordinate_transformations.c:159-176).  s, C: host double[nz]; depth double[ny][nx]; eta double[nt][ny][nx] or
+ * NULL for 0.  No transcendental is involved: the result is the reference's bit for bit.
+ */
+int fimex_amd_vertical_ocean_depth_device(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* s, const double* C,
+                                          double depth_c, const double* d_depth, const double* d_eta, float* d_out, void* stream);
+int fimex_amd_vertical_ocean_depth_host(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* s, const double* C,
+                                        double depth_c, const double* depth, const double* eta, float* out);
+
 /* ----------------------------------- plan building across projections (8f n2) */
 /* The reference calls PROJ.4 (pj_init_plus / pj_transform) here; this library carries its own projections:
  * latlong/longlat, stere, lcc, merc, tmerc, etmerc, utm, laea, aea, geos, omerc, sinu, cea, ortho, aeqd, nsper, ob_tran with o_proj=longlat (radians at this boundary for
