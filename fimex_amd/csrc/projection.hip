@@ -1421,6 +1421,36 @@ void launch_project_axes(const char* projIn, const char* projOut, const double* 
     FA_HIP(hipStreamSynchronize(stream));  // d_axes is released on return
 }
 
+namespace {
+// the delta of mifi_get_vector_reproject_matrix_proj (:458-518): 0.1 % of the distance between neighbouring cells, at the origin
+// and in the middle of the mesh, both taken from the x field in the input projection as the reference does; at(i) reads cell i.
+// Divergence D7: the second probe, cell (ox/2 + 1, oy/2 + 1), lies past the mesh when oy == 2, or ox == 2 and oy <= 4; the
+// reference reads beyond the field there (:469), here the first probe stands alone.
+template <class At>
+double mesh_delta(At at, size_t ox, size_t oy)
+{
+    const double d = 1e-3;
+    double delta;
+    if (ox > 1 && oy > 1) {
+        const size_t ox2 = ox / 2, oy2 = oy / 2;
+        delta = d * (at(ox + 1) - at(0));
+        const size_t far = (oy2 + 1) * ox + ox2 + 1;
+        if (far < ox * oy) {
+            delta += d * (at(far) - at(oy2 * ox + ox2));
+            delta /= 2;
+        }
+    } else if (ox > 1) {
+        delta = d * (at(1) - at(0));
+    } else if (oy > 1) {
+        delta = d * (at(ox) - at(0));
+    } else {
+        const double v = at(0);
+        delta = (v > 1) ? v * d : d;
+    }
+    return std::fabs(delta) < 1e-9 ? d : delta;  // :509-513
+}
+}  // namespace
+
 // mifi_get_vector_reproject_matrix, interpolation.c:719-788 (axes of longitude / latitude type arrive in degrees, :740-745)
 void launch_vector_reproject_matrix(const char* projIn, const char* projOut, const double* h_outXAxis, const double* h_outYAxis,
                                     int xAxisType, int yAxisType, size_t ox, size_t oy, double* d_matrix, hipStream_t stream)
@@ -1438,57 +1468,18 @@ void launch_vector_reproject_matrix(const char* projIn, const char* projOut, con
     // positions of the output mesh in the input projection (:773)
     project_axes_kernel<<<point_blocks(n), kBlock, 0, stream>>>(out, in, d_axes.get(), d_axes.get() + ox, (uint32_t)ox, (uint32_t)oy, d_inX.get(), d_inY.get());
     FA_HIP(hipGetLastError());
-    // delta: 0.1 % of the distance between neighbouring cells, at the origin and in the middle of the mesh, both taken from
-    // the x field as the reference does (:458-513)
     auto at = [&](size_t idx) {
         double v = 0;
         FA_HIP(hipMemcpyAsync(&v, d_inX.get() + idx, sizeof(double), hipMemcpyDeviceToHost, stream));
         FA_HIP(hipStreamSynchronize(stream));
         return v;
     };
-    const double d = 1e-3;
-    double delta;
-    if (ox > 1 && oy > 1) {
-        const size_t ox2 = ox / 2, oy2 = oy / 2;
-        delta = d * (at(ox + 1) - at(0));
-        delta += d * (at((oy2 + 1) * ox + ox2 + 1) - at(oy2 * ox + ox2));
-        delta /= 2;
-    } else if (ox > 1) {
-        delta = d * (at(1) - at(0));
-    } else if (oy > 1) {
-        delta = d * (at(ox) - at(0));
-    } else {
-        const double v = at(0);
-        delta = (v > 1) ? v * d : d;
-    }
-    if (std::fabs(delta) < 1e-9) delta = d;  // :514-518
+    const double delta = mesh_delta(at, ox, oy);
     vector_matrix_kernel<<<point_blocks(n), kBlock, 0, stream>>>(in, out, d_inX.get(), d_inY.get(), d_axes.get(), d_axes.get() + ox, 1, (uint32_t)ox,
                                                                  n, delta, delta, out.kind == kLatLong ? 1 : 0, d_matrix);
     FA_HIP(hipGetLastError());
     FA_HIP(hipStreamSynchronize(stream));  // temporaries are released on return
 }
-
-namespace {
-// the delta of mifi_get_vector_reproject_matrix_proj (:458-518) from the positions in the input projection
-double mesh_delta(const double* inX, size_t ox, size_t oy)
-{
-    const double d = 1e-3;
-    double delta;
-    if (ox > 1 && oy > 1) {
-        const size_t ox2 = ox / 2, oy2 = oy / 2;
-        delta = d * (inX[ox + 1] - inX[0]);
-        delta += d * (inX[(oy2 + 1) * ox + ox2 + 1] - inX[oy2 * ox + ox2]);
-        delta /= 2;
-    } else if (ox > 1) {
-        delta = d * (inX[1] - inX[0]);
-    } else if (oy > 1) {
-        delta = d * (inX[ox] - inX[0]);
-    } else {
-        delta = (inX[0] > 1) ? inX[0] * d : d;
-    }
-    return std::fabs(delta) < 1e-9 ? d : delta;
-}
-}  // namespace
 
 // mifi_get_vector_reproject_matrix_field, interpolation.c:657-717: the mesh is given in the INPUT projection
 void launch_vector_reproject_matrix_field(const char* projIn, const char* projOut, const double* h_inX, const double* h_inY, size_t ox,
@@ -1504,7 +1495,7 @@ void launch_vector_reproject_matrix_field(const char* projIn, const char* projOu
     FA_HIP(hipMemcpyAsync(d_out.get(), d_in.get(), 2 * n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     project_values_kernel<<<point_blocks(n), kBlock, 0, stream>>>(in, out, d_out.get(), d_out.get() + n, n);  // :696
     FA_HIP(hipGetLastError());
-    const double delta = mesh_delta(h_inX, ox, oy);
+    const double delta = mesh_delta([&](size_t idx) { return h_inX[idx]; }, ox, oy);
     vector_matrix_kernel<<<point_blocks(n), kBlock, 0, stream>>>(in, out, d_in.get(), d_in.get() + n, d_out.get(), d_out.get() + n, 0, (uint32_t)ox, n,
                                                                  delta, delta, out.kind == kLatLong ? 1 : 0, d_matrix);
     FA_HIP(hipGetLastError());

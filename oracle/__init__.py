@@ -21,7 +21,14 @@ PROJ_AXIS, LONGITUDE, LATITUDE = 0, 1, 2
 
 
 def build(force=False):
-    """Compile the oracle with gcc (no-op when up to date)."""
+    """Compile the oracle with gcc (no-op when up to date) and, where a reference tree is at hand, the reference's own C code
+    (build_ref).  Returns the oracle's path."""
+    so = _build_oracle(force)
+    build_ref(force)
+    return so
+
+
+def _build_oracle(force=False):
     src = os.path.join(_HERE, "fimex_oracle.c")
     hdr = os.path.join(_HERE, "fimex_oracle.h")
     if (not force and os.path.exists(_SO)
@@ -31,6 +38,32 @@ def build(force=False):
     return _SO
 
 
+_REF_SO = os.path.join(_HERE, "_ref", "libmifi_ref.so")
+_REF_SOURCES = ("src/interpolation.c", "src/vertical_coordinate_transformations.c")
+
+
+def reference_root():
+    """Root of a reference (Fimex) source tree: $FIMEX_REFERENCE_DIR, else /root/reference; None when it holds no sources."""
+    root = os.environ.get("FIMEX_REFERENCE_DIR") or "/root/reference"
+    if all(os.path.isfile(os.path.join(root, s)) for s in _REF_SOURCES):
+        return root
+    return None
+
+
+def build_ref(force=False):
+    """oracle/_ref/libmifi_ref.so: the reference's own C sources, unmodified, with oracle/ref_shim (recipe in the Makefile).
+    Without a reference tree nothing is built and an existing oracle/_ref is left alone.  Returns the path, or None."""
+    root = reference_root()
+    if root is None:
+        return _REF_SO if os.path.exists(_REF_SO) else None
+    deps = [os.path.join(root, s) for s in _REF_SOURCES] + [os.path.join(_HERE, "ref_shim", n) for n in ("ref_shim.c", "proj_api.h")]
+    deps.append(os.path.join(_HERE, "Makefile"))
+    if not force and os.path.exists(_REF_SO) and os.path.getmtime(_REF_SO) >= max(os.path.getmtime(d) for d in deps):
+        return _REF_SO
+    subprocess.check_call(["make", "-C", _HERE, "-B", "_ref/libmifi_ref.so", "REF=" + root], stdout=subprocess.DEVNULL)
+    return _REF_SO
+
+
 _lib = None
 
 
@@ -38,7 +71,7 @@ def lib():
     global _lib
     if _lib is None:
         if not os.path.exists(_SO):
-            build()
+            _build_oracle()
         _lib = ctypes.CDLL(_SO)
         _declare(_lib)
     return _lib
@@ -304,3 +337,16 @@ def nan2bad(a, bad):
     flat = a.reshape(-1)
     lib().orc_nanf2bad(_f(flat), ctypes.cast(flat.ctypes.data + flat.nbytes, _F), bad)
     return a
+
+
+_ref = None
+
+
+def ref():
+    """The reference's own C code (oracle/_ref/libmifi_ref.so, see build_ref) behind a front-end shaped like this module's:
+    an oracle.reference.Reference, or None when the file is absent (no reference tree was at hand when build() ran)."""
+    global _ref
+    if _ref is None and os.path.exists(_REF_SO):
+        from .reference import Reference
+        _ref = Reference(_REF_SO)
+    return _ref

@@ -27,6 +27,16 @@
  *  D6 float -> integer conversion of values beyond the range of long: lround is
  *     unspecified there; LONG_MIN (glibc, x86-64) is kept, then truncated to int
  *     as MetNoFimex::round does (include/fimex/Utils.h:72-75).
+ *  D7 (not in this file: tests/test_oracle_kats.py _rotation_matrix_field and
+ *     fimex_amd/csrc/projection.hip mesh_delta) the rotation matrix's delta
+ *     averages two probes of in_x_field; the second, cell (ox/2+1, oy/2+1), is
+ *     past the ox*oy mesh when oy == 2, or ox == 2 and oy <= 4, and the
+ *     reference reads beyond the field (src/interpolation.c:469, :494).  There
+ *     the first probe stands alone.
+ *
+ * Outside D1, D2, D5 and D7 every function here is bit-identical to the
+ * reference's own object code: tests/test_oracle_vs_reference.py runs both on
+ * the same inputs (oracle/_ref/libmifi_ref.so, recipe in oracle/Makefile).
  */
 #include "fimex_oracle.h"
 

@@ -6,10 +6,12 @@
  * cpu_baseline leg use it, as the checker / the CPU baseline.
  *
  * Every function cites the reference file:line it restates (paths relative to
- * the reference tree).  The reference's own src/interpolation.c cannot be built
- * in this image (it includes PROJ.4's proj_api.h, which is absent), so this
- * restatement is pinned by the reference's own known-answer tests and data
- * fixtures instead (tests/test_oracle_kats.py, tests/golden/).
+ * the reference tree).  The restatement is pinned twice: by the reference's own
+ * known-answer tests and data fixtures (tests/test_oracle_kats.py, tests/golden/),
+ * and bit for bit by the reference's own src/interpolation.c, compiled unmodified
+ * with a stand-in for PROJ.4's proj_api.h (oracle/ref_shim, oracle/Makefile) and
+ * run on the same inputs (tests/test_oracle_vs_reference.py; recorded answers in
+ * tests/golden/reference_answers.npz where no reference tree is at hand).
  *
  * Arithmetic contract: built with -ffp-contract=off, no -ffast-math; every
  * float/double operation is performed in the same type and order as in the

@@ -283,6 +283,26 @@ def test_vector_reproject_matrix_on_the_gpu(fa, pin, pout, xa, ya, types):
     np.testing.assert_allclose(np.cos(got[:, 3]), got[:, 0], atol=1e-15)
 
 
+@pytest.mark.parametrize("mesh", [(1, 1), (1, 9), (9, 1), (2, 2), (3, 2), (40, 2), (2, 3), (2, 4), (2, 5), (3, 3)], ids=lambda m: "%dx%d" % m)
+def test_vector_reproject_matrix_on_small_meshes(fa, mesh):
+    """Every branch of the delta (src/interpolation.c:463-508), and the meshes of divergence D7 (oy == 2, or ox == 2 with
+    oy <= 4), where the reference's second probe is past the mesh: the first probe stands alone, in the library as in the
+    restatement, and nothing beyond the mesh is read.  Same bounds as test_vector_reproject_matrix_on_the_gpu."""
+    ox, oy = mesh
+    for pin, pout, xa, ya, types in ((STERE, GEO, np.linspace(-3, 3, ox), np.linspace(60, 62, oy), (1, 2)),
+                                     (ROT, STERE_OBL, np.linspace(8e5, -8e5, ox), np.linspace(-6e5, 6e5, oy), (0, 0))):
+        got = fa.get_vector_reproject_matrix_host(pin, pout, xa, ya, types[0], types[1]).reshape(-1, 4)
+        want = _rotation_matrix(pin, pout, xa, ya, types[0], types[1]).reshape(-1, 4)
+        np.testing.assert_allclose(got[:, :3], want[:, :3], atol=2e-6)
+        np.testing.assert_allclose(np.hypot(got[:, 0], got[:, 1]), 1.0, atol=1e-14)
+        np.testing.assert_array_equal(got[:, 2], -got[:, 1])
+        if types == (0, 0):
+            xx, yy = np.meshgrid(xa, ya)
+            in_x, in_y = po.transform(pout, pin, xx.ravel(), yy.ravel())
+            field = fa.get_vector_reproject_matrix_field_host(pin, pout, in_x.reshape(oy, ox), in_y.reshape(oy, ox)).reshape(-1, 4)
+            np.testing.assert_allclose(field[:, :3], want[:, :3], atol=2e-6)
+
+
 def test_quarter_turn_rotates_u_into_v(fa):
     """test/testInterpolation.cc:396-453 with the matrix built on the device: lon_0 turned by 90 degrees maps u -> -v, v -> u."""
     p1 = "+ellps=sphere +a=127.4 +e=0 +proj=stere +lat_0=90 +lon_0=0 +lat_ts=60"

@@ -159,13 +159,26 @@ def _rotation_matrix(proj_in, proj_out, out_x_axis, out_y_axis, out_x_type, out_
     return _rotation_matrix_field(proj_in, proj_out, in_x, in_y, out_x, out_y, ox, oy)
 
 
+def second_probe_outside(ox, oy):
+    """D7, from the mesh size alone: cell (ox/2 + 1, oy/2 + 1) of the reference's second delta probe (:469, :494) is past the
+    ox * oy field: oy == 2, or ox == 2 with oy <= 4."""
+    return ox > 1 and oy > 1 and (oy // 2 + 1) * ox + ox // 2 + 1 >= ox * oy
+
+
 def _rotation_matrix_field(proj_in, proj_out, in_x, in_y, out_x, out_y, ox, oy):
-    d = 1e-3
-    assert ox > 1 and oy > 1
-    ox2, oy2 = ox // 2, oy // 2
-    delta = d * (in_x[ox + 1] - in_x[0])                      # :465 / :490 (both use in_x_field)
-    delta2 = d * (in_x[(oy2 + 1) * ox + ox2 + 1] - in_x[oy2 * ox + ox2])
-    delta = (delta + delta2) / 2
+    delta = d = 1e-3
+    if ox > 1 and oy > 1:
+        ox2, oy2 = ox // 2, oy // 2
+        delta = d * (in_x[ox + 1] - in_x[0])                  # :465 / :490 (both use in_x_field)
+        if not second_probe_outside(ox, oy):                  # divergence D7: the reference reads past the field (:469)
+            delta2 = d * (in_x[(oy2 + 1) * ox + ox2 + 1] - in_x[oy2 * ox + ox2])
+            delta = (delta + delta2) / 2
+    elif ox > 1:
+        delta = d * (in_x[1] - in_x[0])                       # :473
+    elif oy > 1:
+        delta = d * (in_x[ox] - in_x[0])                      # :477
+    else:
+        delta = in_x[0] * d if in_x[0] > 1 else d             # :480
     if abs(delta) < 1e-9:
         delta = d
     xdx = po.transform(proj_in, proj_out, in_x + delta, in_y)
