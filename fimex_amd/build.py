@@ -19,6 +19,8 @@ LIB = os.path.join(HERE, "libfimex_amd.so")
 TUNING_LIB = os.path.join(HERE, "libfimex_amd_tuning.so")  # the same sources with -DFIMEX_AMD_TUNING: reads FIMEX_AMD_<NAME> switches
 HOSTLIB = os.path.join(HERE, "libfimex_amd_host.so")
 HOSTCLI = os.path.join(HERE, "host_cli")  # executable of the C++ host mirror (listed in .gitignore by name)
+STENCIL_LIB = os.path.join(HERE, "libstencil_math_host.so")  # csrc/stencil_math.hpp compiled for the CPU (tests/test_stencil_math_host.py)
+STENCIL_SHIM = os.path.join(ROOT, "tests", "stencil_math_host.hip")
 
 DEVICE_SOURCES = ["capi.hip", "regrid.hip", "staged.hip", "staged2.hip", "forward.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip"]
 
@@ -101,10 +103,23 @@ def build_host(force=False):
     return HOSTLIB
 
 
+def build_stencil_host(force=False):
+    """The backward stencil rules the kernels compile (csrc/stencil_math.hpp), for the host only: the tests run it on the CPU, without a GPU."""
+    if force or _newer(STENCIL_LIB, [STENCIL_SHIM] + _headers()):
+        cmd = [_hipcc(), "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC,
+               STENCIL_SHIM, "-o", STENCIL_LIB, "-Wl,-rpath,/opt/rocm/lib"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("stencil shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
+        if r.stderr.strip():
+            sys.stderr.write(r.stderr)
+    return STENCIL_LIB
+
+
 def clean():
     """Removes every built artefact, so that the next build starts from the sources alone."""
     shutil.rmtree(OBJ, ignore_errors=True)
-    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, os.path.join(HERE, "host_cli.so")):
+    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, STENCIL_LIB, os.path.join(HERE, "host_cli.so")):
         if os.path.exists(f):
             os.remove(f)
 
@@ -115,6 +130,7 @@ def build_all(force=False, jobs=4):
     lib = build_device(force=force, jobs=jobs)
     build_device(force=force, jobs=jobs, tuning=True)
     host = build_host(force=force)
+    build_stencil_host(force=force)
     return lib, host
 
 

@@ -133,6 +133,17 @@ constexpr int kBlock = 256;  // 4 waves, one per SIMD
 
 inline size_t ceil_div(size_t a, size_t b) { return (a + b - 1) / b; }
 
+// MIFI_UNDEFINED_F: the quiet NaN every kernel writes for an undefined value
+__host__ __device__ __forceinline__ float undefined_f() { return __builtin_bit_cast(float, 0x7fc00000u); }
+
+// Buffer addressing: a 128-bit descriptor (4 SGPRs) built from wave-uniform values; the per-lane part of an address is one
+// 32-bit byte offset, and an offset at or beyond `bytes` is dropped (loads return zeros, stores do nothing).
+using rsrc_t = __amdgpu_buffer_rsrc_t;
+__device__ __forceinline__ rsrc_t make_rsrc(const void* base, uint32_t bytes)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: set it once per device and kernel
 // (a process may drive several devices through fimex_amd_set_device; the calls are re-entrant)
 inline void allow_dynamic_lds(const void* kernel, size_t bytes)

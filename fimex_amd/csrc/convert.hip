@@ -15,8 +15,6 @@ namespace {
 
 constexpr double kPi = 3.1415926535897932384626433832795;  // MIFI_PI, include/fimex/mifi_constants.h:42
 
-__device__ __forceinline__ float undefined_f() { return __uint_as_float(0x7fc00000u); }
-
 template <bool TO_NAN>
 __device__ __forceinline__ bool hit(float v, float bad) { return TO_NAN ? (v == bad) : isnan(v); }  // :1778 / :1788
 

@@ -26,8 +26,6 @@ namespace fimex_amd {
 
 namespace {
 
-__device__ __forceinline__ float undefined_f() { return __uint_as_float(0x7fc00000u); }
-
 // RoundAndClamp(0, n-1, -1), src/Utils.cc:42-58 (round(): half away from zero)
 __device__ __forceinline__ int64_t round_clamp(double d, int64_t n)
 {

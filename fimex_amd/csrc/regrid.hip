@@ -21,24 +21,15 @@
 // Built with -ffp-contract=off: every multiply and add below is a separate IEEE operation in
 // the same type and order as the reference, so results are bit-identical to the CPU path.
 #include "plan.hpp"
-
-#include <type_traits>
+#include "stencil_math.hpp"
+#include "typed_convert.hpp"
 
 #include <algorithm>
-#include "typed_convert.hpp"
+#include <type_traits>
 
 namespace fimex_amd {
 
 namespace {
-
-__device__ __forceinline__ float undefined_f() { return __uint_as_float(0x7fc00000u); }  // MIFI_UNDEFINED_F
-
-// coordinates beyond this, NaN or inf are "outside" (the reference casts them to int: undefined behaviour)
-__device__ __forceinline__ bool usable(double x, double y)
-{
-    const double lim = 1073741824.0;
-    return (fabs(x) < lim) && (fabs(y) < lim);  // false for NaN
-}
 
 struct PlanCounters {
     unsigned long long undefined;
@@ -46,6 +37,7 @@ struct PlanCounters {
 };
 
 // ---------------------------------------------------------------- plan classification
+// One output cell per lane: classify<STENCIL> (stencil_math.hpp) says which source cells it reads, the entry is encoded from that.
 // src/interpolation.c:864-868
 __global__ void __launch_bounds__(kBlock) classify_nearest(const double* __restrict__ px, const double* __restrict__ py,
                                                            uint32_t n, int64_t ix, int64_t iy,
@@ -53,15 +45,9 @@ __global__ void __launch_bounds__(kBlock) classify_nearest(const double* __restr
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const double x = px[i], y = py[i];
-    uint32_t p = kInvalidPos;
-    if (usable(x, y)) {
-        const int64_t rx = (int64_t)round(x);  // lround: half away from zero
-        const int64_t ry = (int64_t)round(y);
-        if (rx >= 0 && rx < ix && ry >= 0 && ry < iy) p = (uint32_t)(ry * ix + rx);
-    }
-    pos[i] = p;
-    if (p == kInvalidPos) atomicAdd(&counters->undefined, 1ull);
+    const CellNeed c = classify<1>(px[i], py[i], ix, iy);
+    pos[i] = encode_pos(c, ix);
+    if (!c.valid) atomicAdd(&counters->undefined, 1ull);
 }
 
 // src/interpolation.c:883-954 without the z loops
@@ -73,39 +59,13 @@ __global__ void __launch_bounds__(kBlock) classify_bilinear(const double* __rest
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const double x = px[i], y = py[i];
-    uint32_t p = kInvalidPos;
-    float fx = 0.f, fy = 0.f;
-    bool border = false;
-    if (usable(x, y)) {
-        const double flx = floor(x), fly = floor(y);
-        const int64_t x0 = (int64_t)flx, y0 = (int64_t)fly;
-        fx = (float)(x - flx);  // :885, double difference rounded to float
-        fy = (float)(y - fly);  // :888
-        const bool xlin = (0 <= x0) && (x0 + 1 < ix);
-        const bool ylin = (0 <= y0) && (y0 + 1 < iy);
-        if (xlin && ylin) {
-            p = (uint32_t)(y0 * ix + x0);
-        } else if (xlin) {
-            const int64_t ry = (int64_t)round(y);  // :904
-            if (0 <= ry && ry < iy) { p = (uint32_t)(ry * ix + x0); fy = -1.f; border = true; }
-        } else {
-            const int64_t rx = (int64_t)round(x);  // :922
-            if (0 <= rx && rx < ix) {
-                if (ylin) {
-                    p = (uint32_t)(y0 * ix + rx); fx = -1.f; border = true;
-                } else {
-                    const int64_t ry = (int64_t)round(y);  // :935
-                    // the reference tests "ry <= iy" (:936) and then reads past the slice; undefined here
-                    if (0 <= ry && ry < iy) { p = (uint32_t)(ry * ix + rx); fx = -1.f; fy = -1.f; border = true; }
-                }
-            }
-        }
-    }
-    pos[i] = p;
-    xf[i] = fx;
-    yf[i] = fy;
-    if (p == kInvalidPos) atomicAdd(&counters->undefined, 1ull);
-    if (border) atomicAdd(&counters->border, 1ull);
+    const CellNeed c = classify<2>(x, y, ix, iy);
+    const bool oneColumn = c.xa == c.xb, oneRow = c.ya == c.yb;
+    pos[i] = encode_pos(c, ix);
+    xf[i] = encode_frac_bilinear(c, oneColumn, x);
+    yf[i] = encode_frac_bilinear(c, oneRow, y);
+    if (!c.valid) atomicAdd(&counters->undefined, 1ull);
+    else if (oneColumn || oneRow) atomicAdd(&counters->border, 1ull);
 }
 
 // src/interpolation.c:970-976
@@ -117,19 +77,11 @@ __global__ void __launch_bounds__(kBlock) classify_bicubic(const double* __restr
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const double x = px[i], y = py[i];
-    uint32_t p = kInvalidPos;
-    double fx = 0., fy = 0.;
-    if (usable(x, y)) {
-        const double flx = floor(x), fly = floor(y);
-        const int64_t x0 = (int64_t)flx, y0 = (int64_t)fly;
-        fx = x - flx;
-        fy = y - fly;
-        if ((1 <= x0) && (x0 + 2 < ix) && (1 <= y0) && (y0 + 2 < iy)) p = (uint32_t)((y0 - 1) * ix + (x0 - 1));
-    }
-    pos[i] = p;
-    xfd[i] = fx;
-    yfd[i] = fy;
-    if (p == kInvalidPos) atomicAdd(&counters->undefined, 1ull);
+    const CellNeed c = classify<4>(x, y, ix, iy);
+    pos[i] = encode_pos(c, ix);
+    xfd[i] = encode_frac_bicubic(c, x);
+    yfd[i] = encode_frac_bicubic(c, y);
+    if (!c.valid) atomicAdd(&counters->undefined, 1ull);
 }
 
 // ------------------------------------------------------------------------ apply kernels
@@ -167,13 +119,7 @@ __device__ __forceinline__ bool tile_cell(const ApplyArgs& a, uint32_t& cell)
 // wave-uniform values; the per-lane part of an address is one 32-bit byte offset VGPR (plus an
 // immediate), the slice index goes into the scalar offset.  No 64-bit per-lane address arithmetic,
 // which keeps the register budget for loads in flight.  A chunk must span < 4 GiB (checked on the
-// host: kernels with ZC > 1 are only launched when ZC slices fit).
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-
-__device__ __forceinline__ rsrc_t make_rsrc(const float* base, uint32_t bytes)
-{
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, bytes, 0x00020000);
-}
+// host: kernels with ZC > 1 are only launched when ZC slices fit).  rsrc_t / make_rsrc: common.hpp.
 __device__ __forceinline__ float ld(rsrc_t r, uint32_t voff, uint32_t soff)
 {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
@@ -223,12 +169,6 @@ __global__ void __launch_bounds__(kBlock) nearest_apply(ApplyArgs a, const uint3
         st_stream(make_rsrc(o, outBytes), cb, 0, ld(make_rsrc(src, inBytes), pb, 0));
 }
 
-// interior cell, src/interpolation.c:899-900
-__device__ __forceinline__ float bilinear_point(float s00, float s01, float s10, float s11, float xf, float yf)
-{
-    return (1.f - yf) * ((1.f - xf) * s00 + xf * s01) + yf * ((1.f - xf) * s10 + xf * s11);
-}
-
 template <int ZC, bool NT = true>
 __global__ void __launch_bounds__(kBlock) bilinear_apply(ApplyArgs a, const uint32_t* __restrict__ pos,
                                                          const float* __restrict__ xfrac, const float* __restrict__ yfrac)
@@ -240,8 +180,7 @@ __global__ void __launch_bounds__(kBlock) bilinear_apply(ApplyArgs a, const uint
     const uint32_t p = pos[cell];
     const float xf = xfrac[cell], yf = yfrac[cell];
     if (p == kInvalidPos) { write_undefined(a, cell, z0, z1); return; }
-    const bool nnx = (__float_as_uint(xf) >> 31) != 0;
-    const bool nny = (__float_as_uint(yf) >> 31) != 0;
+    const bool nnx = is_nn(xf), nny = is_nn(yf);
     const uint32_t inBytes = (uint32_t)a.inLayer * 4u, outBytes = a.nOut * 4u;
     const float* src = a.in + (size_t)z0 * a.inLayer;
     const float* o = a.out + (size_t)z0 * a.nOut;
@@ -261,7 +200,7 @@ __global__ void __launch_bounds__(kBlock) bilinear_apply(ApplyArgs a, const uint
             }
 #pragma unroll
             for (int k = 0; k < ZC; ++k) {
-                const float r = bilinear_point(s00[k], s01[k], s10[k], s11[k], xf, yf);
+                const float r = bilinear_forms(s00[k], s01[k], s10[k], s11[k], xf, yf).inter;
                 if (NT) st_stream(ro, cb, outBytes * k, r);
                 else st_plain(ro, cb, outBytes * k, r);
             }
@@ -271,18 +210,15 @@ __global__ void __launch_bounds__(kBlock) bilinear_apply(ApplyArgs a, const uint
         for (; z < z1; ++z, src += a.inLayer, o += a.nOut) {
             const rsrc_t rs = make_rsrc(src, inBytes);
             st_stream(make_rsrc(o, outBytes), cb, 0,
-                      bilinear_point(ld(rs, pb, 0), ld(rs, pb + 4u, 0), ld(rs, pb1, 0), ld(rs, pb1 + 4u, 0), xf, yf));
+                      bilinear_forms(ld(rs, pb, 0), ld(rs, pb + 4u, 0), ld(rs, pb1, 0), ld(rs, pb1 + 4u, 0), xf, yf).inter);
         }
     } else {
         // border branches of src/interpolation.c:903-948: a handful of cells on the rim of the domain
         for (uint32_t z = z0; z < z1; ++z, src += a.inLayer, o += a.nOut) {
             const rsrc_t rs = make_rsrc(src, inBytes);
-            const float s00 = ld(rs, pb, 0);
-            float r;
-            if (nnx && nny) r = s00;                                       // :939-942
-            else if (nny) r = (1.f - xf) * s00 + xf * ld(rs, pb + 4u, 0);  // :911
-            else r = (1 - yf) * s00 + (yf * ld(rs, pb1, 0));               // :931
-            st_stream(make_rsrc(o, outBytes), cb, 0, r);
+            const float s00 = ld(rs, pb, 0);  // the one neighbour the entry has is read, the cells it lacks repeat s00
+            const float s01 = nnx ? s00 : ld(rs, pb + 4u, 0), s10 = nny ? s00 : ld(rs, pb1, 0);
+            st_stream(make_rsrc(o, outBytes), cb, 0, bilinear_value(s00, s01, s10, s00, xf, yf));
         }
     }
 }
@@ -305,7 +241,7 @@ __global__ void __launch_bounds__(kBlock) apply_few(ApplyArgs a, const uint32_t*
     const uint32_t y0 = ty * (4u * CELLS) + (threadIdx.x >> 6);
     uint32_t cb[CELLS], pb[CELLS], dxb[CELLS], dyb[CELLS];
     float xf[CELLS], yf[CELLS];
-    bool undef[CELLS], nnx[CELLS], nny[CELLS];
+    bool undef[CELLS];
 #pragma unroll
     for (int k = 0; k < CELLS; ++k) {
         const uint32_t y = y0 + 4u * k;
@@ -317,10 +253,8 @@ __global__ void __launch_bounds__(kBlock) apply_few(ApplyArgs a, const uint32_t*
         yf[k] = (mine && STENCIL == 2) ? yfrac[cell] : 0.f;
         undef[k] = p == kInvalidPos;
         pb[k] = undef[k] ? 0u : p * 4u;
-        nnx[k] = (__float_as_uint(xf[k]) >> 31) != 0;
-        nny[k] = (__float_as_uint(yf[k]) >> 31) != 0;
-        dxb[k] = nnx[k] ? 0u : 4u;           // a missing neighbour repeats the cell itself (its value is not used)
-        dyb[k] = nny[k] ? 0u : a.ix * 4u;
+        dxb[k] = is_nn(xf[k]) ? 0u : 4u;     // a missing neighbour repeats the cell itself (its value is not used)
+        dyb[k] = is_nn(yf[k]) ? 0u : a.ix * 4u;
     }
     const uint32_t inBytes = (uint32_t)a.inLayer * 4u, outBytes = a.nOut * 4u;
     for (uint32_t z = 0; z < a.nz; ++z) {
@@ -337,49 +271,10 @@ __global__ void __launch_bounds__(kBlock) apply_few(ApplyArgs a, const uint32_t*
         }
 #pragma unroll
         for (int k = 0; k < CELLS; ++k) {
-            float r = s00[k];
-            if (STENCIL == 2) {
-                const float top = (1.f - xf[k]) * s00[k] + xf[k] * s01[k];   // :911 when nearest in y
-                const float bot = (1.f - xf[k]) * s10[k] + xf[k] * s11[k];
-                const float inter = (1.f - yf[k]) * top + yf[k] * bot;       // :899-900
-                const float liny = (1 - yf[k]) * s00[k] + (yf[k] * s10[k]);  // :931
-                r = nnx[k] ? (nny[k] ? s00[k] : liny) : (nny[k] ? top : inter);
-            }
+            const float r = STENCIL == 2 ? bilinear_value(s00[k], s01[k], s10[k], s11[k], xf[k], yf[k]) : s00[k];
             st_stream(ro, cb[k], 0, undef[k] ? undefined_f() : r);
         }
     }
-}
-
-// Keys kernel a = -0.5: rows of M/2 (src/interpolation.c:962-968), weights XM / MY (:977-1000)
-__device__ __forceinline__ void cubic_weights(double f, double w[4])
-{
-    const double M[4][4] = {{0.0, 1.0, 0.0, 0.0}, {-0.5, 0.0, 0.5, 0.0}, {1.0, -2.5, 2.0, -0.5}, {-0.5, 1.5, -1.5, 0.5}};
-    double X[4];
-    X[0] = 1;
-    X[1] = f;
-    X[2] = f * f;
-    X[3] = X[2] * f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        double s = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) s += X[j] * M[j][i];
-        w[i] = s;
-    }
-}
-
-// one 4x4 stencil: XMF[i] = sum_j XM[j] * F[j][i] (:1015), out += XMF[i] * MY[i] into the float (:1005,1019)
-__device__ __forceinline__ float bicubic_point(const float f[4][4], const double XM[4], const double MY[4])
-{
-    float acc = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        double xmf = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) xmf += XM[j] * (double)f[i][j];
-        acc = (float)((double)acc + xmf * MY[i]);
-    }
-    return acc;
 }
 
 template <int ZC>
@@ -514,8 +409,8 @@ __global__ void __launch_bounds__(kBlock) typed_apply(TypedArgs t, const uint32_
     const uint32_t cb = cell * E;
     const T fill = static_cast<T>(t.fillOut);  // ScaleValue's newFill_ (Utils.h:456)
     const bool hasBad = t.hasBad != 0;
-    auto rsrc_in = [&](const char* p) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(p), 0, inBytes, 0x00020000); };
-    auto rsrc_out = [&](char* p) { return __builtin_amdgcn_make_buffer_rsrc(p, 0, outBytes, 0x00020000); };
+    auto rsrc_in = [&](const char* p) { return make_rsrc(p, inBytes); };
+    auto rsrc_out = [&](char* p) { return make_rsrc(p, outBytes); };
     auto get = [&](rsrc_t rs, uint32_t off) { return as_float_nan(ld_raw<T>(rs, off, 0), t.bad, hasBad); };
     const uint32_t p = pos[cell];
     if (p == kInvalidPos) {
@@ -524,8 +419,8 @@ __global__ void __launch_bounds__(kBlock) typed_apply(TypedArgs t, const uint32_
     }
     const uint32_t pb = p * E;
     constexpr int ZC = 8;  // slices whose loads are in flight together (one descriptor spans them: ZC * slice bytes < 4 GiB, checked on the host)
-    auto rsrc_in_n = [&](const char* q) { return __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(q), 0, inBytes * ZC, 0x00020000); };
-    auto rsrc_out_n = [&](char* q) { return __builtin_amdgcn_make_buffer_rsrc(q, 0, outBytes * ZC, 0x00020000); };
+    auto rsrc_in_n = [&](const char* q) { return make_rsrc(q, inBytes * ZC); };
+    auto rsrc_out_n = [&](char* q) { return make_rsrc(q, outBytes * ZC); };
     auto getk = [&](rsrc_t rs, uint32_t off, int k) { return as_float_nan(ld_raw<T>(rs, off, inBytes * k), t.bad, hasBad); };
     if (METHOD == 0) {
         uint32_t z = z0;
@@ -541,7 +436,7 @@ __global__ void __launch_bounds__(kBlock) typed_apply(TypedArgs t, const uint32_
             st_raw<T>(rsrc_out(o), cb, 0, from_float_fill<T>(get(rsrc_in(src), pb), fill));
     } else if (METHOD == 1) {
         const float xf = xfrac[cell], yf = yfrac[cell];
-        const bool nnx = (__float_as_uint(xf) >> 31) != 0, nny = (__float_as_uint(yf) >> 31) != 0;
+        const bool nnx = is_nn(xf), nny = is_nn(yf);
         const uint32_t pb1 = pb + a.ix * E;
         uint32_t z = z0;
         if (!(nnx || nny)) {
@@ -557,18 +452,14 @@ __global__ void __launch_bounds__(kBlock) typed_apply(TypedArgs t, const uint32_
                 }
 #pragma unroll
                 for (int k = 0; k < ZC; ++k)
-                    st_raw<T>(ro, cb, outBytes * k, from_float_fill<T>(bilinear_point(s00[k], s01[k], s10[k], s11[k], xf, yf), fill));
+                    st_raw<T>(ro, cb, outBytes * k, from_float_fill<T>(bilinear_forms(s00[k], s01[k], s10[k], s11[k], xf, yf).inter, fill));
             }
         }
         for (; z < z1; ++z, src += inBytes, o += outBytes) {
             const rsrc_t rs = rsrc_in(src);
-            const float s00 = get(rs, pb);
-            float r;
-            if (!(nnx || nny)) r = bilinear_point(s00, get(rs, pb + E), get(rs, pb1), get(rs, pb1 + E), xf, yf);
-            else if (nnx && nny) r = s00;                                   // :939-942
-            else if (nny) r = (1.f - xf) * s00 + xf * get(rs, pb + E);      // :911
-            else r = (1 - yf) * s00 + (yf * get(rs, pb1));                  // :931
-            st_raw<T>(rsrc_out(o), cb, 0, from_float_fill<T>(r, fill));
+            const float s00 = get(rs, pb);  // the neighbours the entry has are read, the cells it lacks repeat s00
+            const float s01 = nnx ? s00 : get(rs, pb + E), s10 = nny ? s00 : get(rs, pb1), s11 = (nnx || nny) ? s00 : get(rs, pb1 + E);
+            st_raw<T>(rsrc_out(o), cb, 0, from_float_fill<T>(bilinear_value(s00, s01, s10, s11, xf, yf), fill));
         }
     } else {
         double XM[4], MY[4];

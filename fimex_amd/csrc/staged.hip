@@ -424,6 +424,8 @@ __global__ void __launch_bounds__(kBlock) staged_apply(StagedArgs a)
             }
 #pragma unroll
             for (int k = 0; k < PER; ++k) {
+                // bilinear_value of stencil_math.hpp, written out: through the helper the 1- and 2-byte instantiations take 2-8 more
+                // VGPRs and lose a wave per SIMD (profiles/stencil_math_resource_usage.md), so this block keeps its own copy
                 const bool nnx = (__float_as_uint(xf[k]) >> 31) != 0, nny = (__float_as_uint(yf[k]) >> 31) != 0;
                 // interior (interpolation.c:899-900); its upper row is the "linear in x, nearest in y" value (:911)
                 const float top = (1.f - xf[k]) * s00[k] + xf[k] * s01[k];
@@ -453,14 +455,7 @@ __global__ void __launch_bounds__(kBlock) staged_apply(StagedArgs a)
 #pragma unroll
                     for (int j = 0; j < 4; ++j) f[i][j] = lds_value<T>(curb, row[k][i] + 4 * j, a.bad, hasBad);
                 }
-                float acc = 0;  // interpolation.c:1005: accumulates into the float output
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    double xmf = 0;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) xmf += XM[k][j] * (double)f[i][j];  // :1015
-                    acc = (float)((double)acc + xmf * MY[k][i]);                    // :1019
-                }
+                const float acc = bicubic_point(f, XM[k], MY[k]);
                 const float r = undef[k] ? undefined_f() : acc;
                 store_result<T>(ro, cellOff[k], r, fillT);
             }

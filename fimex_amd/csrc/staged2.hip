@@ -31,7 +31,7 @@ namespace {
 // fit).  emit == 1: writes the chunk list and every output cell's LDS offsets (16 bits per stencil row, in floats).
 // Where the stencil of an output cell lies: from the caller's positions (plan creation), or -- for the forms of stored types,
 // which are built on first use, long after the positions are gone -- from the gather plan the positions were turned into
-// (regrid.hip: pos = first cell of the stencil, the sign bits of xf / yf = "one column" / "one row", src/interpolation.c:903-948).
+// (entry_need, stencil_math.hpp).
 struct NeedSource {
     const double* px = nullptr;
     const double* py = nullptr;
@@ -44,18 +44,7 @@ template <int STENCIL>
 __device__ __forceinline__ CellNeed need_of(const NeedSource& n, size_t cell, int64_t ix, int64_t iy)
 {
     if (n.px != nullptr) return classify<STENCIL>(n.px[cell], n.py[cell], ix, iy);
-    CellNeed c{};
-    const uint32_t p = n.pos[cell];
-    c.valid = p != kInvalidPos;
-    if (!c.valid) return c;
-    c.ya = (int64_t)(p / (uint32_t)ix);
-    c.xa = (int64_t)p - c.ya * ix;
-    if (STENCIL == 1) { c.xb = c.xa; c.yb = c.ya; }
-    else if (STENCIL == 2) {
-        c.xb = c.xa + ((__float_as_uint(n.xf[cell]) >> 31) ? 0 : 1);
-        c.yb = c.ya + ((__float_as_uint(n.yf[cell]) >> 31) ? 0 : 1);
-    } else { c.xb = c.xa + 3; c.yb = c.ya + 3; }
-    return c;
+    return entry_need<STENCIL>(n.pos[cell], STENCIL == 2 ? n.xf[cell] : 0.f, STENCIL == 2 ? n.yf[cell] : 0.f, ix);
 }
 
 // cpc: source cells per 16-byte chunk (4 for float slices, 8 / 16 for slices of 2- / 1-byte elements); LDS offsets count elements.
@@ -318,22 +307,16 @@ __global__ void __launch_bounds__(NT) staged_apply2(Staged2Args a)
                 if constexpr (STENCIL == 1) {
                     r = ld(p[k]);
                 } else if constexpr (STENCIL == 2) {
-                    const bool nnx = (__float_as_uint(xf[k]) >> 31) != 0, nny = (__float_as_uint(yf[k]) >> 31) != 0;
-                    const uint32_t dx = nnx ? 0u : 1u, dy = nny ? 0u : a.inX;  // a missing neighbour repeats the cell itself
-                    const float s00 = ld(p[k]), s01 = ld(p[k] + dx), s10 = ld(p[k] + dy), s11 = ld(p[k] + dx + dy);
-                    const float top = (1.f - xf[k]) * s00 + xf[k] * s01;
-                    const float bot = (1.f - xf[k]) * s10 + xf[k] * s11;
-                    const float inter = (1.f - yf[k]) * top + yf[k] * bot;
-                    const float liny = (1 - yf[k]) * s00 + (yf[k] * s10);
-                    r = nnx ? (nny ? s00 : liny) : (nny ? top : inter);
+                    const uint32_t dx = is_nn(xf[k]) ? 0u : 1u, dy = is_nn(yf[k]) ? 0u : a.inX;  // a missing neighbour repeats the cell itself
+                    r = bilinear_value(ld(p[k]), ld(p[k] + dx), ld(p[k] + dy), ld(p[k] + dx + dy), xf[k], yf[k]);
                 } else {
                     float f[4][4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
 #pragma unroll
                         for (int j = 0; j < 4; ++j) f[q][j] = ld(p[k] + q * a.inX + j);
-                    float acc = 0;
                     if constexpr (FAST) {
+                        float acc = 0;
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             float xmf = 0;
@@ -341,16 +324,10 @@ __global__ void __launch_bounds__(NT) staged_apply2(Staged2Args a)
                             for (int j = 0; j < 4; ++j) xmf = __builtin_fmaf(XMf[k][j], f[q][j], xmf);
                             acc = __builtin_fmaf(xmf, MYf[k][q], acc);
                         }
+                        r = acc;
                     } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            double xmf = 0;
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) xmf += XM[k][j] * (double)f[q][j];
-                            acc = (float)((double)acc + xmf * MY[k][q]);
-                        }
+                        r = bicubic_point(f, XM[k], MY[k]);
                     }
-                    r = acc;
                 }
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(undef[k] ? undefined_f() : r), ro, cellOff[k], 0, 2);
             }
@@ -377,14 +354,14 @@ __global__ void __launch_bounds__(NT) staged_apply2(Staged2Args a)
     bool plainWave = true;
 #pragma unroll
     for (int k = 0; k < PER; ++k)
-        plainWave = plainWave && !undef[k] && (STENCIL != 2 || ((__float_as_uint(xf[k]) | __float_as_uint(yf[k])) >> 31) == 0);
+        plainWave = plainWave && !undef[k] && (STENCIL != 2 || !(is_nn(xf[k]) || is_nn(yf[k])));
     plainWave = __all(plainWave) != 0;
     // selection masks of the border forms (interpolation.c:903-948) for the other copy: all ones / all zeros per output
     uint32_t mNnx[PER], mNny[PER], mUndef[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
-        mNnx[k] = (uint32_t)((int32_t)__float_as_uint(xf[k]) >> 31);
-        mNny[k] = (uint32_t)((int32_t)__float_as_uint(yf[k]) >> 31);
+        mNnx[k] = nn_mask(xf[k]);
+        mNny[k] = nn_mask(yf[k]);
         mUndef[k] = undef[k] ? 0xFFFFFFFFu : 0u;
     }
     auto pick = [](uint32_t mask, float a, float b) { return __uint_as_float((__float_as_uint(a) & mask) | (__float_as_uint(b) & ~mask)); };
@@ -420,14 +397,10 @@ __global__ void __launch_bounds__(NT) staged_apply2(Staged2Args a)
                 }
     #pragma unroll
                 for (int k = 0; k < PER; ++k) {
-                    // interior (interpolation.c:899-900); its upper row is the "linear in x, nearest in y" value (:911)
-                    const float top = (1.f - xf[k]) * s00[k] + xf[k] * s01[k];
-                    const float bot = (1.f - xf[k]) * s10[k] + xf[k] * s11[k];
-                    const float inter = (1.f - yf[k]) * top + yf[k] * bot;
-                    float r = inter;
-                    if constexpr (!PLAIN) {  // every form is computed, bit masks pick one: no divergent branches in the loop
-                        const float liny = (1 - yf[k]) * s00[k] + (yf[k] * s10[k]);  // nearest in x, linear in y (:931)
-                        r = pick(mNnx[k], pick(mNny[k], s00[k], liny), pick(mNny[k], top, inter));
+                    const BilinearForms b = bilinear_forms(s00[k], s01[k], s10[k], s11[k], xf[k], yf[k]);
+                    float r = b.inter;
+                    if constexpr (!PLAIN) {  // bilinear_select with bit masks: no divergent branches in the loop
+                        r = pick(mNnx[k], pick(mNny[k], s00[k], b.liny), pick(mNny[k], b.top, b.inter));
                         r = pick(mUndef[k], undefined_f(), r);
                     }
                     store_result(__float_as_uint(r), ro, cellOff[k], a.flags);
@@ -468,16 +441,7 @@ __global__ void __launch_bounds__(NT) staged_apply2(Staged2Args a)
     #pragma unroll
                         for (int j = 0; j < 4; ++j) f[r][j] = *reinterpret_cast<const float*>(curb + row[k][r] + 4 * j);
                     }
-                    float acc = 0;  // interpolation.c:1005: accumulates into the float output
-                    {
-    #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            double xmf = 0;
-    #pragma unroll
-                            for (int j = 0; j < 4; ++j) xmf += XM[k][j] * (double)f[r][j];  // :1015
-                            acc = (float)((double)acc + xmf * MY[k][r]);                    // :1019
-                        }
-                    }
+                    const float acc = bicubic_point(f, XM[k], MY[k]);
                     store_result(__float_as_uint(PLAIN ? acc : pick(mUndef[k], undefined_f(), acc)), ro, cellOff[k], a.flags);
                 }
             }
@@ -690,14 +654,8 @@ __global__ void __launch_bounds__(NT) staged_apply2_typed(Staged2Args a, TypedEd
                 if constexpr (STENCIL == 1) {
                     r[q] = ld(p[q]);
                 } else {
-                    const bool nnx = (__float_as_uint(xf[q]) >> 31) != 0, nny = (__float_as_uint(yf[q]) >> 31) != 0;
-                    const uint32_t dx = nnx ? 0u : 1u, dy = nny ? 0u : a.inX;
-                    const float s00 = ld(p[q]), s01 = ld(p[q] + dx), s10 = ld(p[q] + dy), s11 = ld(p[q] + dx + dy);
-                    const float top = (1.f - xf[q]) * s00 + xf[q] * s01;
-                    const float bot = (1.f - xf[q]) * s10 + xf[q] * s11;
-                    const float inter = (1.f - yf[q]) * top + yf[q] * bot;
-                    const float liny = (1 - yf[q]) * s00 + (yf[q] * s10);
-                    r[q] = nnx ? (nny ? s00 : liny) : (nny ? top : inter);
+                    const uint32_t dx = is_nn(xf[q]) ? 0u : 1u, dy = is_nn(yf[q]) ? 0u : a.inX;
+                    r[q] = bilinear_value(ld(p[q]), ld(p[q] + dx), ld(p[q] + dy), ld(p[q] + dx + dy), xf[q], yf[q]);
                 }
                 if (undef[q]) r[q] = undefined_f();
             }
@@ -721,14 +679,14 @@ __global__ void __launch_bounds__(NT) staged_apply2_typed(Staged2Args a, TypedEd
     bool plainWave = true;
 #pragma unroll
     for (int q = 0; q < PER; ++q)
-        plainWave = plainWave && !undef[q] && (STENCIL != 2 || ((__float_as_uint(xf[q]) | __float_as_uint(yf[q])) >> 31) == 0);
+        plainWave = plainWave && !undef[q] && (STENCIL != 2 || !(is_nn(xf[q]) || is_nn(yf[q])));
     plainWave = __all(plainWave) != 0;
     uint32_t mNnx[PER], mNny[PER], mUndef[PER];
     uint32_t rowA[PER][STENCIL], rowS[PER][STENCIL];  // bilinear: aligned byte offset of a stencil row's pair, and its shift operand
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
-        mNnx[q] = (uint32_t)((int32_t)__float_as_uint(xf[q]) >> 31);
-        mNny[q] = (uint32_t)((int32_t)__float_as_uint(yf[q]) >> 31);
+        mNnx[q] = nn_mask(xf[q]);
+        mNny[q] = nn_mask(yf[q]);
         mUndef[q] = undef[q] ? 0xFFFFFFFFu : 0u;
 #pragma unroll
         for (int i = 0; i < STENCIL; ++i) { rowA[q][i] = row[q][i] & ~3u; rowS[q][i] = row[q][i] << 3; }
@@ -772,20 +730,17 @@ __global__ void __launch_bounds__(NT) staged_apply2_typed(Staged2Args a, TypedEd
                 }
 #pragma unroll
                 for (int q = 0; q < PER; ++q) {
-                    const float top = (1.f - xf[q]) * s00[q] + xf[q] * s01[q];
-                    const float bot = (1.f - xf[q]) * s10[q] + xf[q] * s11[q];
-                    const float inter = (1.f - yf[q]) * top + yf[q] * bot;
-                    r[q] = inter;
+                    const BilinearForms b = bilinear_forms(s00[q], s01[q], s10[q], s11[q], xf[q], yf[q]);
+                    r[q] = b.inter;
                     if constexpr (PLAIN) {  // interior cell: undefined iff one of the four is the fill value (mifi_bad2nanf, then NaN spreads)
                         // (the stored elements are integers, exact in float, and so is a fill value that can occur among them: the
                         // product of the four differences is zero iff one element is the fill value -- one comparison and one
                         // selection per output instead of four of each; without a fill value the product is NaN and never zero)
                         const float anyBad = ((s00[q] - badCmp) * (s01[q] - badCmp)) * ((s10[q] - badCmp) * (s11[q] - badCmp));
-                        r[q] = (anyBad == 0.f) ? undefined_f() : inter;
+                        r[q] = (anyBad == 0.f) ? undefined_f() : b.inter;
                     }
                     if constexpr (!PLAIN) {
-                        const float liny = (1 - yf[q]) * s00[q] + (yf[q] * s10[q]);
-                        r[q] = pick(mNnx[q], pick(mNny[q], s00[q], liny), pick(mNny[q], top, inter));
+                        r[q] = pick(mNnx[q], pick(mNny[q], s00[q], b.liny), pick(mNny[q], b.top, b.inter));
                         r[q] = pick(mUndef[q], undefined_f(), r[q]);
                     }
                 }

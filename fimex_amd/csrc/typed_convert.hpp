@@ -3,13 +3,11 @@
 // src/CDMInterpolator.cc:115-124.
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "common.hpp"
 
 #include <type_traits>
 
 namespace fimex_amd {
-
-__device__ __forceinline__ float undefined_value_f() { return __uint_as_float(0x7fc00000u); }
 
 // T -> float is Data::asFloat() = static_cast<float> per element (src/DataImpl.h:99,132,384-389; include/fimex/Utils.h:94-116),
 // then mifi_bad2nanf with the fill value narrowed to float (src/interpolation.c:1775-1783; a NaN fill value changes nothing)
@@ -17,7 +15,7 @@ template <typename T>
 __device__ __forceinline__ float as_float_nan(T v, float bad, bool hasBad)
 {
     const float f = (float)v;
-    return (hasBad && f == bad) ? undefined_value_f() : f;
+    return (hasBad && f == bad) ? undefined_f() : f;
 }
 
 // MetNoFimex::round(double) (include/fimex/Utils.h:72-75): lround, then long -> int.  Outside the range of long the

@@ -19,8 +19,6 @@ namespace fimex_amd {
 
 namespace {
 
-__device__ __forceinline__ float undefined_f() { return __uint_as_float(0x7fc00000u); }  // MIFI_UNDEFINED_F
-
 struct VintArgs {
     Levels in, out;         // out.kind < 0: fixed levels (level1)
     const double* level1;   // device, [nzo]
