@@ -141,6 +141,13 @@ SYMBOLS = {
     "fimex_amd_vertical_standard_pressure_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _D, ctypes.c_double, _F]),
     "fimex_amd_vertical_ocean_depth_device": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, _Z, _D, _D, ctypes.c_double, _V, _V, _V, _V]),
     "fimex_amd_vertical_ocean_depth_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, _Z, _D, _D, ctypes.c_double, _D, _D, _F]),
+    "fimex_amd_griddistance_device": (ctypes.c_int, [_Z, _Z, _V, _V, _V, _V, _V]),
+    "fimex_amd_griddistance_host": (ctypes.c_int, [_Z, _Z, _D, _D, _F, _F]),
+    "fimex_amd_vertical_velocity_device": (ctypes.c_int, [_Z, _Z, _Z, _Z, ctypes.c_double, ctypes.c_double, _V, _V, _D, _D, _V, _V, _V, _V, _V,
+                                                          _V, _V]),
+    "fimex_amd_vertical_velocity_host": (ctypes.c_int, [_Z, _Z, _Z, _Z, ctypes.c_double, ctypes.c_double, _F, _F, _D, _D, _F, _F, _F, _F, _F, _F]),
+    "fimex_amd_omega_to_vertical_wind_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V, _V, _V]),
+    "fimex_amd_omega_to_vertical_wind_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F, _F, _F]),
     "fimex_amd_project_values_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z]),
     "fimex_amd_project_values_device": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _V, _V, _Z, _V]),
     "fimex_amd_project_axes_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z, _Z, _D, _D]),
@@ -706,6 +713,58 @@ def vertical_ocean_depth_device(generation, nx, ny, nt, s, C, depth_c, d_depth, 
     ca, cp = _opt(_f64, _dp, C)
     nz = sa.size if sa is not None else 0
     _check(load().fimex_amd_vertical_ocean_depth_device(generation, nx, ny, nz, nt, sp, cp, depth_c, d_depth, d_eta, d_out, stream))
+
+
+def griddistance_host(lonVals, latVals):
+    """mifi_griddistance: lon / lat [ny][nx] in degrees -> (gridDistX, gridDistY) float32 [ny][nx] in m.  A grid of one point raises,
+    as the reference returns MIFI_ERROR for it."""
+    lo, la = _f64(lonVals), _f64(latVals)
+    ny, nx = lo.shape
+    gx, gy = np.empty((ny, nx), np.float32), np.empty((ny, nx), np.float32)
+    _check(load().fimex_amd_griddistance_host(nx, ny, _dp(lo.reshape(-1)), _dp(la.reshape(-1)), _fp(gx.reshape(-1)), _fp(gy.reshape(-1))))
+    return gx, gy
+
+
+def griddistance_device(nx, ny, d_lon, d_lat, d_gridDistX, d_gridDistY, stream=0):
+    """The same on device pointers; only enqueues on `stream`."""
+    _check(load().fimex_amd_griddistance_device(nx, ny, d_lon, d_lat, d_gridDistX, d_gridDistY, stream))
+
+
+def vertical_velocity_host(nx, ny, nt, dx, dy, gridDistX, gridDistY, ap, b, zs, ps, u, v, t):
+    """mifi_compute_vertical_velocity for nt time steps on host arrays: float32 [nt][nz][ny][nx].  ap (Pa) and b hold nz doubles; zs
+    [ny][nx]; ps (Pa) [nt][ny][nx]; u, v, t [nt][nz][ny][nx]."""
+    apa, app = _opt(_f64, _dp, ap)
+    ba, bp = _opt(_f64, _dp, b)
+    nz = apa.size if apa is not None else 0
+    arrays = [_opt(_f32, _fp, a) for a in (gridDistX, gridDistY, zs, ps, u, v, t)]
+    out = np.empty((nt, nz, ny, nx), np.float32)
+    _check(load().fimex_amd_vertical_velocity_host(nx, ny, nz, nt, dx, dy, arrays[0][1], arrays[1][1], app, bp, *[a[1] for a in arrays[2:]],
+                                                   _fp(out.reshape(-1))))
+    return out
+
+
+def vertical_velocity_device(nx, ny, nt, dx, dy, d_gridDistX, d_gridDistY, ap, b, d_zs, d_ps, d_u, d_v, d_t, d_w, stream=0):
+    """The same on device pointers; only enqueues on `stream`.  ap and b stay host arrays."""
+    apa, app = _opt(_f64, _dp, ap)
+    ba, bp = _opt(_f64, _dp, b)
+    nz = apa.size if apa is not None else 0
+    _check(load().fimex_amd_vertical_velocity_device(nx, ny, nz, nt, dx, dy, d_gridDistX, d_gridDistY, app, bp, d_zs, d_ps, d_u, d_v, d_t, d_w,
+                                                     stream))
+
+
+def omega_to_vertical_wind_host(pressure, nx, ny, nt, omega, t):
+    """OmegaVerticalConverter (omega2vwind) on host arrays: float32 [nt][nz][ny][nx]; the pressure unit of omega is that of the level
+    description."""
+    oa, op = _opt(_f32, _fp, omega)
+    ta, tp = _opt(_f32, _fp, t)
+    out = np.empty((nt, pressure.nz, ny, nx), np.float32)
+    _check(load().fimex_amd_omega_to_vertical_wind_host(_levels_ref(pressure), nx, ny, nt, op, tp, _fp(out.reshape(-1))))
+    return out
+
+
+def omega_to_vertical_wind_device(pressure, nx, ny, nt, d_omega, d_t, d_w, stream=0):
+    """The same on device pointers; d_w may be d_omega (in place).  Only enqueues on `stream`."""
+    _check(load().fimex_amd_omega_to_vertical_wind_device(_levels_ref(pressure), nx, ny, nt, d_omega, d_t, d_w, stream))
 
 
 def project_values_host(proj_input, proj_output, x, y):

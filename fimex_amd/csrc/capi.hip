@@ -1424,3 +1424,159 @@ int fimex_amd_vertical_ocean_depth_host(int generation, size_t nx, size_t ny, si
 }
 
 }  // extern "C"
+
+// ---- vertical velocity on model levels (8f n7)
+namespace {
+
+// true: the reference's "no grid" case of one point, which writes zeros and returns MIFI_ERROR
+bool check_griddistance_call(size_t nx, size_t ny, const double* lon, const double* lat, const float* distX, const float* distY)
+{
+    FA_REQUIRE(nx > 0 && ny > 0, "empty grid (nx * ny == 0)");
+    FA_REQUIRE(lon != nullptr && lat != nullptr, "NULL longitude or latitude");
+    FA_REQUIRE(distX != nullptr && distY != nullptr, "NULL output buffer");
+    const size_t n = nx * ny;
+    FA_REQUIRE(distX + n <= distY || distY + n <= distX, "gridDistX overlaps gridDistY");
+    for (const float* out : {distX, distY})
+        require_no_overlap(out, n * sizeof(float), {{lon, n * sizeof(double), "the longitudes"}, {lat, n * sizeof(double), "the latitudes"}});
+    return n == 1;
+}
+
+void check_velocity_call(size_t nx, size_t ny, size_t nz, size_t nt, const float* distX, const float* distY, const double* ap, const double* b,
+                         const float* zs, const float* ps, const float* u, const float* v, const float* t, const float* w)
+{
+    // the reference reads outside its arrays on such grids
+    FA_REQUIRE(nx >= 3 && ny >= 3, "the vertical velocity needs nx >= 3 and ny >= 3 (got " + std::to_string(nx) + " x " + std::to_string(ny) + ")");
+    FA_REQUIRE(nz > 0, "no levels (nz == 0)");
+    FA_REQUIRE(ap != nullptr && b != nullptr, "NULL ap[nz] or b[nz]");
+    FA_REQUIRE(distX != nullptr && distY != nullptr, "NULL grid distance");
+    FA_REQUIRE(nt == 0 || (zs != nullptr && ps != nullptr), "NULL orography or surface pressure");
+    FA_REQUIRE(nt == 0 || (u != nullptr && v != nullptr && t != nullptr), "NULL wind or temperature");
+    FA_REQUIRE(nt == 0 || w != nullptr, "NULL output buffer");
+    const size_t plane = nx * ny, vol = nt * nz * plane * sizeof(float);
+    require_no_overlap(w, vol, {{distX, plane * sizeof(float), "gridDistX"}, {distY, plane * sizeof(float), "gridDistY"},
+                                {zs, plane * sizeof(float), "the orography"}, {ps, nt * plane * sizeof(float), "the surface pressure"},
+                                {u, vol, "the x wind"}, {v, vol, "the y wind"}, {t, vol, "the air temperature"}});
+}
+
+// false: nothing to do
+bool check_omega_call(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* omega, const float* t,
+                      const float* w)
+{
+    using namespace fimex_amd;
+    const bool nonEmpty = nx * ny * nt > 0;
+    check_vertical_levels(pressure, "pressure", nonEmpty);
+    if (!nonEmpty) return false;
+    FA_REQUIRE(pressure->nz > 0, "no levels (nz == 0)");
+    FA_REQUIRE(omega != nullptr, "NULL omega");
+    FA_REQUIRE(t != nullptr, "NULL air temperature");
+    FA_REQUIRE(w != nullptr, "NULL output buffer");
+    const size_t cells = nx * ny * nt, vol = cells * pressure->nz * sizeof(float);
+    if (w != omega) require_no_overlap(w, vol, {{omega, vol, "omega (other than in place)"}});
+    require_no_overlap(w, vol, {{t, vol, "the air temperature"}});
+    require_no_overlap_with_levels(w, vol, *pressure, cells);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fimex_amd_griddistance_device(size_t nx, size_t ny, const double* d_lon, const double* d_lat, float* d_gridDistX, float* d_gridDistY,
+                                  void* stream)
+{
+    bool noGrid = false;
+    const int rc = c_guard([&] {
+        noGrid = check_griddistance_call(nx, ny, d_lon, d_lat, d_gridDistX, d_gridDistY);
+        (void)current_device_checked();
+        launch_griddistance(nx, ny, d_lon, d_lat, d_gridDistX, d_gridDistY, as_stream(stream));
+        if (noGrid) set_last_error("a grid of one point has no grid distance: zeros written");
+    });
+    return noGrid ? FIMEX_AMD_ERROR : rc;
+}
+
+int fimex_amd_griddistance_host(size_t nx, size_t ny, const double* lon, const double* lat, float* gridDistX, float* gridDistY)
+{
+    bool noGrid = false;
+    const int rc = c_guard([&] {
+        noGrid = check_griddistance_call(nx, ny, lon, lat, gridDistX, gridDistY);
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t n = nx * ny;
+        DeviceArray<double> d(2 * n);
+        DeviceArray<float> out(2 * n);
+        host_to_device(d.get(), lon, n * sizeof(double), stream.get());
+        host_to_device(d.get() + n, lat, n * sizeof(double), stream.get());
+        launch_griddistance(nx, ny, d.get(), d.get() + n, out.get(), out.get() + n, stream.get());
+        device_to_host(gridDistX, out.get(), n * sizeof(float), stream.get());
+        device_to_host(gridDistY, out.get() + n, n * sizeof(float), stream.get());
+        stream.sync();
+        if (noGrid) set_last_error("a grid of one point has no grid distance: zeros written");
+    });
+    return noGrid ? FIMEX_AMD_ERROR : rc;
+}
+
+int fimex_amd_vertical_velocity_device(size_t nx, size_t ny, size_t nz, size_t nt, double dx, double dy, const float* d_gridDistX,
+                                       const float* d_gridDistY, const double* ap, const double* b, const float* d_zs, const float* d_ps,
+                                       const float* d_u, const float* d_v, const float* d_t, float* d_w, void* stream)
+{
+    return c_guard([&] {
+        check_velocity_call(nx, ny, nz, nt, d_gridDistX, d_gridDistY, ap, b, d_zs, d_ps, d_u, d_v, d_t, d_w);
+        if (nt == 0) return;
+        (void)current_device_checked();
+        launch_vertical_velocity(nx, ny, nz, nt, dx, dy, d_gridDistX, d_gridDistY, ap, b, d_zs, d_ps, d_u, d_v, d_t, d_w, as_stream(stream));
+    });
+}
+
+int fimex_amd_vertical_velocity_host(size_t nx, size_t ny, size_t nz, size_t nt, double dx, double dy, const float* gridDistX,
+                                     const float* gridDistY, const double* ap, const double* b, const float* zs, const float* ps, const float* u,
+                                     const float* v, const float* t, float* w)
+{
+    return c_guard([&] {
+        check_velocity_call(nx, ny, nz, nt, gridDistX, gridDistY, ap, b, zs, ps, u, v, t, w);
+        if (nt == 0) return;
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t plane = nx * ny, vol = nt * nz * plane;
+        DeviceArray<float> d_gx, d_gy, d_zs, d_ps, d_u, d_v, d_t, d_w(vol);
+        const float* gx = to_device(d_gx, gridDistX, plane, stream.get());
+        const float* gy = to_device(d_gy, gridDistY, plane, stream.get());
+        const float* dzs = to_device(d_zs, zs, plane, stream.get());
+        const float* dps = to_device(d_ps, ps, nt * plane, stream.get());
+        const float* du = to_device(d_u, u, vol, stream.get());
+        const float* dv = to_device(d_v, v, vol, stream.get());
+        const float* dt = to_device(d_t, t, vol, stream.get());
+        launch_vertical_velocity(nx, ny, nz, nt, dx, dy, gx, gy, ap, b, dzs, dps, du, dv, dt, d_w.get(), stream.get());
+        device_to_host(w, d_w.get(), d_w.bytes(), stream.get());
+        stream.sync();
+    });
+}
+
+int fimex_amd_omega_to_vertical_wind_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* d_omega,
+                                            const float* d_t, float* d_w, void* stream)
+{
+    return c_guard([&] {
+        if (!check_omega_call(pressure, nx, ny, nt, d_omega, d_t, d_w)) return;
+        (void)current_device_checked();
+        launch_omega_to_vertical_wind(*pressure, nx, ny, nt, d_omega, d_t, d_w, as_stream(stream));
+    });
+}
+
+int fimex_amd_omega_to_vertical_wind_host(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* omega,
+                                          const float* t, float* w)
+{
+    return c_guard([&] {
+        if (!check_omega_call(pressure, nx, ny, nt, omega, t, w)) return;
+        (void)current_device_checked();
+        ScopedStream stream;
+        const size_t plane = nx * ny, vol = nt * pressure->nz * plane;
+        HostLevels l(*pressure, plane, nt, stream.get());
+        DeviceArray<float> d_omega, d_t;
+        float* dw = to_device(d_omega, omega, vol, stream.get());  // converted in place, as the reference does
+        const float* dt = to_device(d_t, t, vol, stream.get());
+        launch_omega_to_vertical_wind(l.d, nx, ny, nt, dw, dt, dw, stream.get());
+        device_to_host(w, dw, vol * sizeof(float), stream.get());
+        stream.sync();
+    });
+}
+
+}  // extern "C"

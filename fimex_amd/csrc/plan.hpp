@@ -203,6 +203,14 @@ void launch_vertical_standard(bool toPressure, const fimex_amd_vertical_levels& 
 void launch_vertical_ocean_depth(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* h_s, const double* h_C, double depth_c,
                                  const double* d_depth, const double* d_eta, float* d_out, hipStream_t stream);
 
+// vertical_velocity.hip: grid distances, the vertical velocity on model levels, omega to vertical wind
+void launch_griddistance(size_t nx, size_t ny, const double* d_lon, const double* d_lat, float* d_distX, float* d_distY, hipStream_t stream);
+void launch_vertical_velocity(size_t nx, size_t ny, size_t nz, size_t nt, double dx, double dy, const float* d_distX, const float* d_distY,
+                              const double* h_ap, const double* h_b, const float* d_zs, const float* d_ps, const float* d_u, const float* d_v,
+                              const float* d_t, float* d_w, hipStream_t stream);
+void launch_omega_to_vertical_wind(const fimex_amd_vertical_levels& pressure, size_t nx, size_t ny, size_t nt, const float* d_omega,
+                                   const float* d_t, float* d_w, hipStream_t stream);
+
 // projection.hip: pj_transform-level plan building on the device
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);
 void launch_project_axes(const char* projIn, const char* projOut, const double* h_xAxis, const double* h_yAxis, size_t ix, size_t iy,

@@ -501,6 +501,73 @@ int fimex_amd_vertical_ocean_depth_device(int generation, size_t nx, size_t ny, 
 int fimex_amd_vertical_ocean_depth_host(int generation, size_t nx, size_t ny, size_t nz, size_t nt, const double* s, const double* C,
                                         double depth_c, const double* depth, const double* eta, float* out);
 
+/* ------------------------------------ vertical velocity on model levels (8f n7) */
+/* What CDMProcessor::addVerticalVelocity (src/CDMProcessor.cc:158-318, :515-530) computes per time step, and the omega2vwind
+ * conversion of CDMPressureConversions.  Layouts as above: x fastest, [nt][nz][ny][nx].  The *_device entries only enqueue work
+ * on the stream and never synchronise it; the *_host entries take host buffers for everything.  ap and b are host double[nz] in
+ * both. */
+
+/**
+ * mifi_griddistance (src/interpolation.c:1539-1595): lon, lat double[ny][nx] in degrees -> gridDistX, gridDistY float[ny][nx] in
+ * m, the great-circle distance (float)(6371000 * acos(sin(la0) * sin(la1) + cos(la0) * cos(la1) * cos(lo1 - lo0))) of cell
+ * p = i + nx * j to its right neighbour p + 1 (X) and to the next row's cell p + nx (Y), every angle multiplied by DEG_TO_RAD
+ * = .017453292519943296 first, all in double.  The last column repeats the column before it.  The last row is filled as the
+ * reference fills it, from i = 0 upward with g[p] = g[p - ny] (not p - nx): for i >= ny the source lies in the last row itself
+ * and holds what was written there a moment earlier, so the value of cell i is that of cell i mod ny of the last row.
+ * nx == 1 or ny == 1: the distance to the next point along the line in both outputs, the last point repeating the one before.
+ * nx * ny == 1: zeros are written and -1 is returned, as the reference does.  The outputs must not overlap each other or an
+ * input.  The device's sin, cos and acos are not the host's: a result is within 2^-23 * |d| + 6371000 * 2^-49 / sin(d / 6371000)
+ * of the reference's.
+ */
+int fimex_amd_griddistance_device(size_t nx, size_t ny, const double* d_lon, const double* d_lat, float* d_gridDistX, float* d_gridDistY,
+                                  void* stream);
+int fimex_amd_griddistance_host(size_t nx, size_t ny, const double* lon, const double* lat, float* gridDistX, float* gridDistY);
+
+/**
+ * mifi_compute_vertical_velocity (src/interpolation.c:1597-1773) for nt time steps: upward_air_velocity_ml in m/s on hybrid
+ * levels, index 0 at the top.  dx, dy: the grid spacing of the projection axes in m; gridDistX, gridDistY float[ny][nx] from
+ * fimex_amd_griddistance_*; ap (Pa) and b: host double[nz] of the full levels; zs [ny][nx] orography in m; ps [nt][ny][nx] in Pa;
+ * u, v (m/s), t (K) and w [nt][nz][ny][nx].  Everything is computed in double, floats promoted on read, with
+ * R = 8.31432 / 0.0289644 and g = 9.80665:
+ *   per column   mapRatioX = gridDistX / dx, mapRatioY = gridDistY / dy, rhx = 1 / mapRatioX, rhy = 1 / mapRatioY,
+ *                rhxy = rhx * rhy, rdx_2 = 1 / (2 * dx), rdy_2 = 1 / (2 * dy)
+ *   half levels  ah[0] = bh[0] = 0, ah[nz] = 0, bh[nz] = 1, for k = nz-1 .. 1: ah[k] = 2 * ap[k] - ah[k+1], bh[k] = 2 * b[k] - bh[k+1]
+ *   levels k>=1  pm = ah[k] + bh[k] * ps, pp = ah[k+1] + bh[k+1] * ps, dp = pp - pm, dlnp = log(pp / pm), alfa = 1 - pm * dlnp / dp
+ *   hydrostatic  from the surface upward, sum = zs * g: rt = R * t, z[k] = sum + rt * alfa, sum += rt * dlnp
+ *   divergence   from k = 1 downward, sum = 0, in the interior 1 <= i < nx-1, 1 <= j < ny-1, with uu = mapRatioY * u * dp and
+ *                vv = mapRatioX * v * dp of the neighbour cells:
+ *                  div = rhxy * (rdx_2 * (uu[+1] - uu[-1]) + rdy_2 * (vv[+nx] - vv[-nx]))
+ *                  w1 = R * t * (dlnp * sum + alfa * div) / dp,  w2 = rhx * rdx_2 * (z[+1] - z[-1]) + rhy * rdy_2 * (z[+nx] - z[-nx])
+ *                  w = (float)((w1 + w2) / g),  sum = sum + div
+ *                so sum never holds level k's own divergence when w of level k is taken, and level 0's is never added
+ *   borders      rows j = 0 and ny-1 copy rows 1 and ny-2 for 1 <= i < nx-1, then columns i = 0 and nx-1 copy columns 1 and nx-2
+ *                for every j; w at k = 0 is +0
+ * NaN, non-positive pressures and zero distances are not treated specially: IEEE arithmetic decides.  The device's log is not
+ * the host's (about 2^-51 relative), so w is the reference's within 2^-23 * |w| plus that error times the magnitude of the terms
+ * that cancel in w1 + w2; almost every cell is bit-identical.
+ * One divergence: for nx < 3, ny < 3 or nz < 1 the reference reads outside its arrays or uninitialised memory; these entries
+ * return -1 with a message.  w must not overlap an input.  A scratch of (nz - 1) * ny * nx doubles is taken from the stream's
+ * memory pool for the duration of the call.
+ */
+int fimex_amd_vertical_velocity_device(size_t nx, size_t ny, size_t nz, size_t nt, double dx, double dy, const float* d_gridDistX,
+                                       const float* d_gridDistY, const double* ap, const double* b, const float* d_zs, const float* d_ps,
+                                       const float* d_u, const float* d_v, const float* d_t, float* d_w, void* stream);
+int fimex_amd_vertical_velocity_host(size_t nx, size_t ny, size_t nz, size_t nt, double dx, double dy, const float* gridDistX,
+                                     const float* gridDistY, const double* ap, const double* b, const float* zs, const float* ps, const float* u,
+                                     const float* v, const float* t, float* w);
+
+/**
+ * OmegaVerticalConverter::getDataSlice (src/CDMPressureConversions.cc:417-427) with mifi_omega_to_vertical_wind_f
+ * (src/vertical_coordinate_transformations.c:195-209): w = ((mR_g * omega) * t) / p in float, mR_g = (float)(-8.31432 /
+ * (9.80665 * 0.0289644)), p the level's pressure as float (what fimex_amd_vertical_levels_* would write), in the pressure unit
+ * of omega (hPa and hPa/s in the reference).  omega, t and w [nt][pressure->nz][ny][nx]; w may be omega itself (the reference
+ * converts in place) but must not overlap anything else.  The result is the reference's bit for bit.
+ */
+int fimex_amd_omega_to_vertical_wind_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* d_omega,
+                                            const float* d_t, float* d_w, void* stream);
+int fimex_amd_omega_to_vertical_wind_host(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* omega,
+                                          const float* t, float* w);
+
 /* ----------------------------------- plan building across projections (8f n2) */
 /* The reference calls PROJ.4 (pj_init_plus / pj_transform) here; this library carries its own projections:
  * latlong/longlat, stere, lcc, merc, tmerc, etmerc, utm, laea, aea, geos, omerc, sinu, cea, ortho, aeqd, nsper, ob_tran with o_proj=longlat (radians at this boundary for
