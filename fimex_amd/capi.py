@@ -148,6 +148,15 @@ SYMBOLS = {
     "fimex_amd_vertical_velocity_host": (ctypes.c_int, [_Z, _Z, _Z, _Z, ctypes.c_double, ctypes.c_double, _F, _F, _D, _D, _F, _F, _F, _F, _F, _F]),
     "fimex_amd_omega_to_vertical_wind_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V, _V, _V]),
     "fimex_amd_omega_to_vertical_wind_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F, _F, _F]),
+    "fimex_amd_border_smooth_device": (ctypes.c_int, [_V, _V, _V, _Z, _Z, _Z, _Z, _Z, ctypes.c_int, _V]),
+    "fimex_amd_border_smooth_host": (ctypes.c_int, [_F, _F, _F, _Z, _Z, _Z, _Z, _Z, ctypes.c_int]),
+    "fimex_amd_overlay_device": (ctypes.c_int, [_V, _V, _V, _Z, _V]),
+    "fimex_amd_overlay_host": (ctypes.c_int, [_F, _F, _F, _Z]),
+    "fimex_amd_merge_plan_create": (ctypes.c_int, [_V, _V, _V, _Z, _Z, ctypes.c_int, ctypes.POINTER(_V)]),
+    "fimex_amd_merge_plan_destroy": (ctypes.c_int, [_V]),
+    "fimex_amd_merge_apply_device": (ctypes.c_int, [_V, _V, _V, _Z, _V, _V]),
+    "fimex_amd_merge_apply_host": (ctypes.c_int, [_V, _F, _F, _Z, _F]),
+    "fimex_amd_merge_apply_chain_device": (ctypes.c_int, [_V, _V, _V, _Z, _V, _V]),
     "fimex_amd_project_values_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z]),
     "fimex_amd_project_values_device": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _V, _V, _Z, _V]),
     "fimex_amd_project_axes_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z, _Z, _D, _D]),
@@ -765,6 +774,79 @@ def omega_to_vertical_wind_host(pressure, nx, ny, nt, omega, t):
 def omega_to_vertical_wind_device(pressure, nx, ny, nt, d_omega, d_t, d_w, stream=0):
     """The same on device pointers; d_w may be d_omega (in place).  Only enqueues on `stream`."""
     _check(load().fimex_amd_omega_to_vertical_wind_device(_levels_ref(pressure), nx, ny, nt, d_omega, d_t, d_w, stream))
+
+
+def border_smooth_host(inner, outerOnInner, transitionWidth=5, borderWidth=2, useOuterIfInnerUndefined=True):
+    """CDMBorderSmoothing::getDataSlice with the linear smoothing: two [nz][ny][nx] (or [ny][nx]) float32 host arrays -> the smoothed one."""
+    i, o = _f32(inner), _f32(outerOnInner)
+    if i.shape != o.shape or i.ndim < 2:
+        raise ValueError("inner and outer differ in shape")
+    ny, nx = i.shape[-2:]
+    out = np.empty_like(i)
+    _check(load().fimex_amd_border_smooth_host(_fp(i), _fp(o), _fp(out), nx, ny, i.size // max(nx * ny, 1), transitionWidth, borderWidth,
+                                               int(bool(useOuterIfInnerUndefined))))
+    return out
+
+
+def border_smooth_device(d_inner, d_outerOnInner, d_out, nx, ny, nz, transitionWidth=5, borderWidth=2, useOuterIfInnerUndefined=True, stream=0):
+    _check(load().fimex_amd_border_smooth_device(d_inner, d_outerOnInner, d_out, nx, ny, nz, transitionWidth, borderWidth,
+                                                 int(bool(useOuterIfInnerUndefined)), stream))
+
+
+def overlay_host(top, base):
+    """CDMOverlay::getDataSlice: top where it is defined, else base."""
+    t, b = _f32(top), _f32(base)
+    if t.shape != b.shape:
+        raise ValueError("top and base differ in shape")
+    out = np.empty_like(t)
+    _check(load().fimex_amd_overlay_host(_fp(t), _fp(b), _fp(out), t.size))
+    return out
+
+
+def overlay_device(d_top, d_base, d_out, n, stream=0):
+    _check(load().fimex_amd_overlay_device(d_top, d_base, d_out, n, stream))
+
+
+class MergePlan:
+    """fimex_amd_merge_plan: CDMMerger's data path on three backward RegridPlans (outer -> inner grid, inner -> target,
+    outer -> target), which it keeps alive."""
+
+    def __init__(self, outerToInner, innerToTarget, outerToTarget, transitionWidth=5, borderWidth=2, useOuterIfInnerUndefined=True):
+        self._plans = (outerToInner, innerToTarget, outerToTarget)
+        self._h = _V()
+        self.outX, self.outY = innerToTarget.outX, innerToTarget.outY
+        _check(load().fimex_amd_merge_plan_create(outerToInner._h, innerToTarget._h, outerToTarget._h, transitionWidth, borderWidth,
+                                                  int(bool(useOuterIfInnerUndefined)), ctypes.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            load().fimex_amd_merge_plan_destroy(self._h)
+            self._h = _V()
+        self._plans = ()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown: module globals may be gone already
+            pass
+
+    def apply_host(self, inner, outer):
+        """CDMMerger::getDataSlice: inner [nz][iy][ix], outer [nz][oy][ox] float32 host arrays -> [nz][ty][tx]."""
+        oi = self._plans[0]
+        i, o = _f32(inner).ravel(), _f32(outer).ravel()
+        nz = i.size // (oi.outX * oi.outY)
+        if i.size != nz * oi.outX * oi.outY or o.size != nz * oi.inX * oi.inY:
+            raise ValueError("inner and outer do not hold the same number of whole slices")
+        out = np.empty((nz, self.outY, self.outX), dtype=np.float32)
+        _check(load().fimex_amd_merge_apply_host(self._h, _fp(i), _fp(o), nz, _fp(out)))
+        return out
+
+    def apply_device(self, d_inner, d_outer, nz, d_out, stream=0):
+        _check(load().fimex_amd_merge_apply_device(self._h, d_inner, d_outer, nz, d_out, stream))
+
+    def apply_chain_device(self, d_inner, d_outer, nz, d_out, stream=0):
+        """The same merge by the plain applies and the two elementwise kernels (cross-check and yardstick of the fused kernels)."""
+        _check(load().fimex_amd_merge_apply_chain_device(self._h, d_inner, d_outer, nz, d_out, stream))
 
 
 def project_values_host(proj_input, proj_output, x, y):

@@ -1,0 +1,479 @@
+// Grid merging: the arithmetic of CDMMerger, that is CDMBorderSmoothing::getDataSlice (src/CDMBorderSmoothing.cc:
+// 129-139) with CDMBorderSmoothing_Linear::operator() (src/CDMBorderSmoothing_Linear.cc:41-85) and CDMOverlay::getDataSlice
+// (src/CDMOverlay.cc:82-86), between the three regrids of CDMMergerPrivate::makeCDM (src/CDMMerger.cc:212-227).  DESIGN.md 6.8.
+//   border_smooth_kernel  S = smooth(I, OI) on a batch of slices, one alias-safe pass
+//   overlay_kernel        out = isnan(top) ? base : top, one alias-safe pass
+//   merge_smooth_kernel   steps 1 and 2 fused: a lane per inner cell evaluates the outer->inner plan entry only where the smoothing
+//                         reads the outer (frame, transition band, undefined inner) and writes S
+//   merge_overlay_kernel  steps 3 and 4 fused: a lane per target cell evaluates the inner->target entry on S and the outer->target
+//                         entry on O only where S does not reach
+// A lane owns one cell of a kTileX x kTileY tile and keeps its class (smoothing) or its plan entries (regrid) in registers over the
+// z loop; kAhead slices are in flight per lane.  Every slice has its own buffer descriptor, so a batch of any length is addressed
+// with 32-bit lane offsets (a slice holds fewer than 2^30 cells, plan.hpp).  The plan entries and the stencil arithmetic are those
+// of stencil_math.hpp.  Built with -ffp-contract=off: I + alpha * diff is a multiply and an add, as in the reference.
+#include "plan.hpp"
+#include "stencil_math.hpp"
+
+#include <cmath>
+
+namespace fimex_amd {
+
+namespace {
+
+constexpr int kTileX = 64, kTileY = 4;  // a wave per row
+static_assert(kTileX * kTileY == kBlock, "a tile is one workgroup");
+constexpr int kAhead = 4;               // slices whose loads are in flight together
+
+__device__ __forceinline__ float ld(rsrc_t r, uint32_t voff)
+{
+    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
+}
+// written once and never re-read by the kernel that writes it: non-temporal (aux = 2), as the applies of regrid.hip
+__device__ __forceinline__ void st_stream(rsrc_t r, uint32_t voff, float v)
+{
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, 0, 2);
+}
+__device__ __forceinline__ void st_plain(rsrc_t r, uint32_t voff, float v)
+{
+    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, 0, 0);
+}
+
+// ---- CDMBorderSmoothing_Linear::operator() (:41-85), split into what depends on the cell and what depends on the values.
+// size_t arithmetic that wraps, as the reference's: xmax2 = nx - bw and xmin2 = xmax2 - tw may wrap, and the comparisons decide
+// the branch on the wrapped values.
+enum : int { kOuter = 0, kInner = 1, kBlend = 2 };
+struct SmoothClass {
+    int kind;
+    double alpha;  // kBlend: divided by the transition width and clamped (:79-83)
+};
+
+__device__ __forceinline__ double dist(double dx, double dy) { return sqrt(dx * dx + dy * dy); }  // :33-35
+
+__device__ __forceinline__ SmoothClass smooth_class(uint64_t x, uint64_t y, uint64_t nx, uint64_t ny, uint64_t tw, uint64_t bw)
+{
+    const uint64_t xmin1 = bw, xmax1 = xmin1 + tw;      // :46
+    const uint64_t ymin1 = bw, ymax1 = ymin1 + tw;      // :47
+    const uint64_t xmax2 = nx - bw, xmin2 = xmax2 - tw;  // :48
+    const uint64_t ymax2 = ny - bw, ymin2 = ymax2 - tw;  // :49
+    SmoothClass c{kOuter, 0.};
+    if (x < xmin1 || x >= xmax2 || y < ymin1 || y >= ymax2) return c;  // :52
+    c.kind = kInner;
+    if (x >= xmax1 && x < xmin2 && y >= ymax1 && y < ymin2) return c;  // :54
+    c.kind = kBlend;
+    double alpha = 0;
+    if (x < xmax1) {  // :60-78
+        if (y < ymax1) alpha = dist((double)(xmax1 - x), (double)(ymax1 - y));
+        else if (y >= ymin2) alpha = dist((double)(xmax1 - x), (double)(y - ymin2));
+        else alpha = (double)(xmax1 - x);
+    } else if (x >= xmin2) {
+        if (y < ymax1) alpha = dist((double)(x - xmin2), (double)(ymax1 - y));
+        else if (y >= ymin2) alpha = dist((double)(x - xmin2), (double)(y - ymin2));
+        else alpha = (double)(x - xmin2);
+    } else if (y < ymax1) {
+        alpha = (double)(ymax1 - y);
+    } else if (y >= ymin2) {
+        alpha = (double)(y - ymin2);
+    }
+    alpha /= (double)tw;
+    if (alpha > 1) alpha = 1;
+    else if (alpha < 0) alpha = 0;
+    c.alpha = alpha;
+    return c;
+}
+
+// true: smooth_value reads the outer value for this inner value
+__device__ __forceinline__ bool needs_outer(const SmoothClass& c, float inner, bool useOuter)
+{
+    return inner != inner ? useOuter : c.kind != kInner;
+}
+
+// CDMBorderSmoothing.cc:129-139 on one cell; outer is read only where needs_outer says so
+__device__ __forceinline__ float smooth_value(const SmoothClass& c, float inner, float outer, bool useOuter)
+{
+    if (inner != inner) return useOuter ? outer : undefined_f();  // :132-133
+    if (c.kind == kInner || outer != outer) return inner;         // :134-135, Linear :54-55
+    if (c.kind == kOuter) return outer;                           // Linear :52-53
+    const double valueI = (double)inner, valueO = (double)outer;
+    const double diff = valueO - valueI;  // :56
+    if (diff == 0) return outer;          // :57-58
+    return (float)(valueI + c.alpha * diff);
+}
+
+struct SmoothArgs {
+    const float *inner, *outer;  // [nz][ny][nx]
+    float* out;
+    uint32_t nx, ny, nz, zPerBlock;
+    uint64_t tw, bw;
+    int useOuter;
+};
+
+// every lane reads its cell of both inputs before it writes it: out may be either of them
+__global__ void __launch_bounds__(kBlock) border_smooth_kernel(const SmoothArgs a)
+{
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= a.nx || y >= a.ny) return;
+    const SmoothClass c = smooth_class(x, y, a.nx, a.ny, a.tw, a.bw);
+    const bool useOuter = a.useOuter != 0;
+    const size_t plane = (size_t)a.nx * a.ny;
+    const uint32_t planeBytes = (uint32_t)plane * 4u, cb = (y * a.nx + x) * 4u;
+    uint32_t z = blockIdx.z * a.zPerBlock;
+    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
+    for (; z + kAhead <= z1; z += kAhead) {
+        float vi[kAhead], vo[kAhead];
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) {
+            vi[k] = ld(make_rsrc(a.inner + (size_t)(z + k) * plane, planeBytes), cb);
+            vo[k] = ld(make_rsrc(a.outer + (size_t)(z + k) * plane, planeBytes), cb);
+        }
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, smooth_value(c, vi[k], vo[k], useOuter));
+    }
+    for (; z < z1; ++z) {
+        const float vi = ld(make_rsrc(a.inner + (size_t)z * plane, planeBytes), cb), vo = ld(make_rsrc(a.outer + (size_t)z * plane, planeBytes), cb);
+        st_plain(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, smooth_value(c, vi, vo, useOuter));
+    }
+}
+
+// CDMOverlay.cc:82-86.  A workgroup takes kAhead * kBlock consecutive values; a lane reads its values before it writes them.
+__global__ void __launch_bounds__(kBlock) overlay_kernel(const float* top, const float* base, float* out, size_t n)
+{
+    const size_t i0 = (size_t)blockIdx.x * (kAhead * kBlock) + threadIdx.x;
+    float t[kAhead], b[kAhead];
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k) {
+        const size_t i = i0 + (size_t)k * kBlock;
+        t[k] = i < n ? top[i] : 0.f;
+        b[k] = i < n ? base[i] : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k) {
+        const size_t i = i0 + (size_t)k * kBlock;
+        if (i < n) out[i] = t[k] != t[k] ? b[k] : t[k];
+    }
+}
+
+// ---- one entry of a backward plan, decoded once per cell and evaluated slice by slice (stencil_math.hpp)
+struct PlanRef {
+    const uint32_t* pos;
+    const float *xf, *yf;
+    const double *xfd, *yfd;
+    uint32_t ix;       // source row length
+    uint32_t inBytes;  // bytes of a source slice
+    size_t inLayer;    // cells of a source slice
+};
+
+// An undefined entry (kInvalidPos) is given a lane offset beyond every slice and zero strides: the buffer range check drops its
+// loads, so it reads nothing and the lane stays on the common path; the value is then replaced by NaN.
+constexpr uint32_t kDropped = 0xFFFFFFFCu;  // a slice has fewer than 2^30 cells: its bytes end below this offset
+
+template <int STENCIL>
+struct Entry;
+
+template <>
+struct Entry<1> {
+    uint32_t pb;
+    bool valid;
+    __device__ __forceinline__ Entry(const PlanRef& p, uint32_t cell)
+    {
+        const uint32_t q = p.pos[cell];
+        valid = q != kInvalidPos;
+        pb = valid ? q * 4u : kDropped;
+    }
+    __device__ __forceinline__ float value(rsrc_t rs) const
+    {
+        const float v = ld(rs, pb);
+        return valid ? v : undefined_f();
+    }
+};
+
+template <>
+struct Entry<2> {
+    uint32_t pb, dxb, dyb;
+    float xf, yf;
+    bool valid;
+    __device__ __forceinline__ Entry(const PlanRef& p, uint32_t cell)
+    {
+        const uint32_t q = p.pos[cell];
+        xf = p.xf[cell];
+        yf = p.yf[cell];
+        valid = q != kInvalidPos;
+        pb = valid ? q * 4u : kDropped;
+        dxb = (!valid || is_nn(xf)) ? 0u : 4u;  // a missing neighbour repeats the cell itself (its value is not selected)
+        dyb = (!valid || is_nn(yf)) ? 0u : p.ix * 4u;
+    }
+    __device__ __forceinline__ float value(rsrc_t rs) const
+    {
+        const float s00 = ld(rs, pb), s01 = ld(rs, pb + dxb), s10 = ld(rs, pb + dyb), s11 = ld(rs, pb + dxb + dyb);
+        const float v = bilinear_value(s00, s01, s10, s11, xf, yf);
+        return valid ? v : undefined_f();
+    }
+};
+
+template <>
+struct Entry<4> {
+    uint32_t pb, colb, rowb;  // byte steps to the next column and row of the stencil
+    bool valid;
+    double XM[4], MY[4];
+    __device__ __forceinline__ Entry(const PlanRef& p, uint32_t cell)
+    {
+        const uint32_t q = p.pos[cell];
+        valid = q != kInvalidPos;
+        pb = valid ? q * 4u : kDropped;
+        colb = valid ? 4u : 0u;
+        rowb = valid ? p.ix * 4u : 0u;
+        cubic_weights(p.xfd[cell], XM);
+        cubic_weights(p.yfd[cell], MY);
+    }
+    __device__ __forceinline__ float value(rsrc_t rs) const
+    {
+        float f[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) f[i][j] = ld(rs, pb + i * rowb + j * colb);
+        const float v = bicubic_point(f, XM, MY);
+        return valid ? v : undefined_f();
+    }
+};
+
+struct MergeSmoothArgs {
+    PlanRef oi;           // outer -> inner grid
+    const float *inner;   // [nz][ny][nx]
+    const float *outer;   // [nz] source slices of oi
+    float* s;             // [nz][ny][nx]
+    uint32_t nx, ny, nz, zPerBlock;
+    uint64_t tw, bw;
+    int useOuter;
+};
+
+// steps 1 and 2: S = smooth(I, regrid(O -> inner grid)), the regrid evaluated only where the smoothing reads it
+template <int STENCIL>
+__global__ void __launch_bounds__(kBlock) merge_smooth_kernel(const MergeSmoothArgs a)
+{
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= a.nx || y >= a.ny) return;
+    const uint32_t cell = y * a.nx + x, cb = cell * 4u;
+    const SmoothClass c = smooth_class(x, y, a.nx, a.ny, a.tw, a.bw);
+    const Entry<STENCIL> e(a.oi, cell);
+    const bool useOuter = a.useOuter != 0;
+    const size_t plane = (size_t)a.nx * a.ny;
+    const uint32_t planeBytes = (uint32_t)plane * 4u;
+    uint32_t z = blockIdx.z * a.zPerBlock;
+    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
+    for (; z + kAhead <= z1; z += kAhead) {
+        float vi[kAhead], vo[kAhead];
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) vi[k] = ld(make_rsrc(a.inner + (size_t)(z + k) * plane, planeBytes), cb);
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k)
+            vo[k] = needs_outer(c, vi[k], useOuter) ? e.value(make_rsrc(a.outer + (size_t)(z + k) * a.oi.inLayer, a.oi.inBytes)) : 0.f;
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.s + (size_t)(z + k) * plane, planeBytes), cb, smooth_value(c, vi[k], vo[k], useOuter));
+    }
+    for (; z < z1; ++z) {
+        const float vi = ld(make_rsrc(a.inner + (size_t)z * plane, planeBytes), cb);
+        const float vo = needs_outer(c, vi, useOuter) ? e.value(make_rsrc(a.outer + (size_t)z * a.oi.inLayer, a.oi.inBytes)) : 0.f;
+        st_plain(make_rsrc(a.s + (size_t)z * plane, planeBytes), cb, smooth_value(c, vi, vo, useOuter));
+    }
+}
+
+struct MergeOverlayArgs {
+    PlanRef st;          // smoothed inner -> target
+    PlanRef ot;          // outer -> target
+    const float *s;      // [nz] source slices of st
+    const float *outer;  // [nz] source slices of ot
+    float* out;          // [nz][ny][nx]
+    uint32_t nx, ny, nz, zPerBlock;
+};
+
+// steps 3 and 4: out = regrid(S -> target) where that is defined, else regrid(O -> target); an invalid inner -> target entry
+// issues no load from S, and the outer -> target entry is evaluated only where the first value is NaN
+template <int ST, int OT>
+__global__ void __launch_bounds__(kBlock) merge_overlay_kernel(const MergeOverlayArgs a)
+{
+    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
+    if (x >= a.nx || y >= a.ny) return;
+    const uint32_t cell = y * a.nx + x, cb = cell * 4u;
+    const Entry<ST> es(a.st, cell);
+    const Entry<OT> eo(a.ot, cell);
+    const size_t plane = (size_t)a.nx * a.ny;
+    const uint32_t planeBytes = (uint32_t)plane * 4u;
+    uint32_t z = blockIdx.z * a.zPerBlock;
+    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
+    for (; z + kAhead <= z1; z += kAhead) {
+        float v[kAhead];
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) v[k] = es.value(make_rsrc(a.s + (size_t)(z + k) * a.st.inLayer, a.st.inBytes));
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k)
+            if (v[k] != v[k]) v[k] = eo.value(make_rsrc(a.outer + (size_t)(z + k) * a.ot.inLayer, a.ot.inBytes));
+#pragma unroll
+        for (int k = 0; k < kAhead; ++k) st_stream(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, v[k]);
+    }
+    for (; z < z1; ++z) {
+        float v = es.value(make_rsrc(a.s + (size_t)z * a.st.inLayer, a.st.inBytes));
+        if (v != v) v = eo.value(make_rsrc(a.outer + (size_t)z * a.ot.inLayer, a.ot.inBytes));
+        st_stream(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, v);
+    }
+}
+
+// tiles of one slice in x and y, chunks of slices in z: enough workgroups to fill the device, chunks long enough to amortise the
+// per-cell set-up (class, plan entries)
+dim3 tile_grid(size_t nx, size_t ny, size_t nz, uint32_t& zPerBlock)
+{
+    FA_REQUIRE(nx * ny <= kMaxSliceCells, "a slice must have fewer than 2^30 cells");
+    FA_REQUIRE(nz <= 0xFFFFFFFFu, "too many slices");
+    const size_t tilesX = ceil_div(nx, kTileX), tilesY = ceil_div(ny, kTileY);
+    FA_REQUIRE(tilesY <= 65535, "grid too tall for one launch");
+    const size_t wantBlocks = 256 * 8 * 4;
+    size_t chunks = ceil_div(wantBlocks, tilesX * tilesY);
+    if (chunks > nz) chunks = nz;
+    size_t zpb = ceil_div(nz, chunks);
+    zpb = ceil_div(zpb, kAhead) * kAhead;
+    if (ceil_div(nz, zpb) > 65535) zpb = ceil_div(nz, (size_t)65535);
+    zPerBlock = (uint32_t)zpb;
+    return dim3((uint32_t)tilesX, (uint32_t)tilesY, (uint32_t)ceil_div(nz, zpb));
+}
+
+int stencil_of(const fimex_amd_regrid_plan& p)
+{
+    switch (p.kind) {
+    case PlanKind::Nearest: return 1;
+    case PlanKind::Bilinear: return 2;
+    case PlanKind::Bicubic: return 4;
+    default: throw Error("merge: not a backward plan");
+    }
+}
+
+PlanRef plan_ref(const fimex_amd_regrid_plan& p)
+{
+    PlanRef r{};
+    r.pos = p.pos.get();
+    r.xf = p.xf.get();
+    r.yf = p.yf.get();
+    r.xfd = p.xfd.get();
+    r.yfd = p.yfd.get();
+    r.ix = (uint32_t)p.inX;
+    r.inLayer = p.inX * p.inY;
+    r.inBytes = (uint32_t)(r.inLayer * 4);
+    return r;
+}
+
+template <int ST>
+void launch_overlay_st(int ot, dim3 grid, const MergeOverlayArgs& a, hipStream_t stream)
+{
+    const dim3 block(kTileX, kTileY, 1);
+    if (ot == 1) merge_overlay_kernel<ST, 1><<<grid, block, 0, stream>>>(a);
+    else if (ot == 2) merge_overlay_kernel<ST, 2><<<grid, block, 0, stream>>>(a);
+    else merge_overlay_kernel<ST, 4><<<grid, block, 0, stream>>>(a);
+}
+
+// stream-ordered float scratch of one call, freed on the stream behind the kernels that use it
+class FloatScratch {
+public:
+    FloatScratch(size_t floats, hipStream_t stream) : stream_(stream)
+    {
+        if (floats) FA_HIP(hipMallocAsync(reinterpret_cast<void**>(&p_), floats * sizeof(float), stream));
+    }
+    ~FloatScratch() { if (p_) (void)hipFreeAsync(p_, stream_); }
+    FloatScratch(const FloatScratch&) = delete;
+    FloatScratch& operator=(const FloatScratch&) = delete;
+    float* get() const { return p_; }
+
+private:
+    float* p_ = nullptr;
+    hipStream_t stream_;
+};
+
+}  // namespace
+
+// every argument has been checked (capi.hip)
+void launch_border_smooth(const float* d_inner, const float* d_outerOnInner, float* d_out, size_t nx, size_t ny, size_t nz, size_t transitionWidth,
+                          size_t borderWidth, bool useOuter, hipStream_t stream)
+{
+    if (nz == 0) return;
+    SmoothArgs a{};
+    const dim3 grid = tile_grid(nx, ny, nz, a.zPerBlock);
+    a.inner = d_inner;
+    a.outer = d_outerOnInner;
+    a.out = d_out;
+    a.nx = (uint32_t)nx;
+    a.ny = (uint32_t)ny;
+    a.nz = (uint32_t)nz;
+    a.tw = transitionWidth;
+    a.bw = borderWidth;
+    a.useOuter = useOuter ? 1 : 0;
+    border_smooth_kernel<<<grid, dim3(kTileX, kTileY, 1), 0, stream>>>(a);
+    FA_HIP(hipGetLastError());
+}
+
+void launch_overlay(const float* d_top, const float* d_base, float* d_out, size_t n, hipStream_t stream)
+{
+    if (n == 0) return;
+    const size_t blocks = ceil_div(n, (size_t)kAhead * kBlock);
+    FA_REQUIRE(blocks <= 0x7fffffffu, "too many values for one launch");
+    overlay_kernel<<<(uint32_t)blocks, kBlock, 0, stream>>>(d_top, d_base, d_out, n);
+    FA_HIP(hipGetLastError());
+}
+
+void launch_merge_fused(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream)
+{
+    if (nz == 0) return;
+    const fimex_amd_regrid_plan &oi = *m.outerToInner, &st = *m.innerToTarget, &ot = *m.outerToTarget;
+    const size_t innerCells = oi.outX * oi.outY;
+    FloatScratch s(nz * innerCells, stream);
+    const dim3 block(kTileX, kTileY, 1);
+    {
+        MergeSmoothArgs a{};
+        const dim3 grid = tile_grid(oi.outX, oi.outY, nz, a.zPerBlock);
+        a.oi = plan_ref(oi);
+        a.inner = d_inner;
+        a.outer = d_outer;
+        a.s = s.get();
+        a.nx = (uint32_t)oi.outX;
+        a.ny = (uint32_t)oi.outY;
+        a.nz = (uint32_t)nz;
+        a.tw = m.transitionWidth;
+        a.bw = m.borderWidth;
+        a.useOuter = m.useOuter ? 1 : 0;
+        switch (stencil_of(oi)) {
+        case 1: merge_smooth_kernel<1><<<grid, block, 0, stream>>>(a); break;
+        case 2: merge_smooth_kernel<2><<<grid, block, 0, stream>>>(a); break;
+        default: merge_smooth_kernel<4><<<grid, block, 0, stream>>>(a); break;
+        }
+        FA_HIP(hipGetLastError());
+    }
+    MergeOverlayArgs a{};
+    const dim3 grid = tile_grid(st.outX, st.outY, nz, a.zPerBlock);
+    a.st = plan_ref(st);
+    a.ot = plan_ref(ot);
+    a.s = s.get();
+    a.outer = d_outer;
+    a.out = d_out;
+    a.nx = (uint32_t)st.outX;
+    a.ny = (uint32_t)st.outY;
+    a.nz = (uint32_t)nz;
+    const int otStencil = stencil_of(ot);
+    switch (stencil_of(st)) {
+    case 1: launch_overlay_st<1>(otStencil, grid, a, stream); break;
+    case 2: launch_overlay_st<2>(otStencil, grid, a, stream); break;
+    default: launch_overlay_st<4>(otStencil, grid, a, stream); break;
+    }
+    FA_HIP(hipGetLastError());
+}
+
+// The same four steps as the reference runs them: three full applies and the two elementwise kernels on temporaries
+void launch_merge_chain(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream)
+{
+    if (nz == 0) return;
+    const fimex_amd_regrid_plan &oi = *m.outerToInner, &st = *m.innerToTarget, &ot = *m.outerToTarget;
+    const size_t innerCells = oi.outX * oi.outY, targetCells = st.outX * st.outY;
+    FloatScratch s(nz * innerCells, stream), top(nz * targetCells, stream);
+    apply_plan_device(oi, d_outer, nz, s.get(), stream);                                                               // step 1
+    launch_border_smooth(d_inner, s.get(), s.get(), oi.outX, oi.outY, nz, m.transitionWidth, m.borderWidth, m.useOuter, stream);  // step 2
+    apply_plan_device(st, s.get(), nz, top.get(), stream);                                                             // step 3
+    apply_plan_device(ot, d_outer, nz, d_out, stream);
+    launch_overlay(top.get(), d_out, d_out, nz * targetCells, stream);                                                 // step 4
+}
+
+}  // namespace fimex_amd

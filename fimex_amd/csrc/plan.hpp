@@ -137,6 +137,15 @@ struct fimex_amd_vector_plan {
     fimex_amd::DeviceArray<double> phi;      // m3
 };
 
+// CDMMerger's data path (merge.hip): three backward plans borrowed from the caller and the parameters of
+// CDMBorderSmoothing_LinearFactory
+struct fimex_amd_merge_plan {
+    int device = 0;
+    const fimex_amd_regrid_plan *outerToInner = nullptr, *innerToTarget = nullptr, *outerToTarget = nullptr;
+    size_t transitionWidth = 5, borderWidth = 2;
+    bool useOuter = true;  // setUseOuterIfInnerUndefined
+};
+
 namespace fimex_amd {
 
 // regrid.hip
@@ -210,6 +219,13 @@ void launch_vertical_velocity(size_t nx, size_t ny, size_t nz, size_t nt, double
                               const float* d_t, float* d_w, hipStream_t stream);
 void launch_omega_to_vertical_wind(const fimex_amd_vertical_levels& pressure, size_t nx, size_t ny, size_t nt, const float* d_omega,
                                    const float* d_t, float* d_w, hipStream_t stream);
+
+// merge.hip: border smoothing, overlay, and CDMMerger's four steps fused or as a chain of the existing applies
+void launch_border_smooth(const float* d_inner, const float* d_outerOnInner, float* d_out, size_t nx, size_t ny, size_t nz, size_t transitionWidth,
+                          size_t borderWidth, bool useOuter, hipStream_t stream);
+void launch_overlay(const float* d_top, const float* d_base, float* d_out, size_t n, hipStream_t stream);
+void launch_merge_fused(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream);
+void launch_merge_chain(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream);
 
 // projection.hip: pj_transform-level plan building on the device
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);

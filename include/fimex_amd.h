@@ -568,6 +568,59 @@ int fimex_amd_omega_to_vertical_wind_device(const fimex_amd_vertical_levels* pre
 int fimex_amd_omega_to_vertical_wind_host(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* omega,
                                           const float* t, float* w);
 
+/* ------------------------------------------------------------ grid merging (8f n8) */
+/* CDMMerger's data path for float interpolation arrays (NaN = undefined), src/CDMMerger.cc:212-227:
+ *   1  OI  = regrid(outer -> inner grid)              (CDMBorderSmoothing's interpolator; bilinear inside CDMMerger)
+ *   2  S   = smooth(inner, OI)                        (CDMBorderSmoothing::getDataSlice)
+ *   3  ST  = regrid(S -> target), OT = regrid(outer -> target)
+ *   4  out = isnan(ST) ? OT : ST                      (CDMOverlay::getDataSlice)
+ * Every step is the reference's arithmetic operation by operation; the results are the reference's bit for bit for variables
+ * stored as float with scale 1 and offset 0 (a double variable is narrowed to float before the blend of step 2 here, after it in
+ * the reference).  Packed variables (the reference rounds them to the stored type after
+ * steps 1, 2 and 3) and vector pairs (the interpolators rotate them) go step by step through the elementwise entries below,
+ * fimex_amd_regrid_apply_typed_device and the rotation entries. */
+/**
+ * CDMBorderSmoothing::getDataSlice (src/CDMBorderSmoothing.cc:129-139) with CDMBorderSmoothing_Linear::operator()
+ * (src/CDMBorderSmoothing_Linear.cc:41-85) on [nz][ny][nx] slices: an undefined inner value gives the outer one
+ * (useOuterIfInnerUndefined) or NaN, an undefined outer value the inner one; otherwise the outer value in the frame of
+ * borderWidth cells, a linear blend over the next transitionWidth cells (the Euclidean distance in the corners) and the inner
+ * value inside.  The cell classes follow the reference's size_t arithmetic, wrap-around included (grids narrower than
+ * 2 * borderWidth + transitionWidth).  transitionWidth == 0, nx == 0 or ny == 0 is an error; nz == 0 does nothing.
+ * out may be inner or outerOnInner itself, but must not overlap either otherwise.
+ */
+int fimex_amd_border_smooth_device(const float* d_inner, const float* d_outerOnInner, float* d_out, size_t nx, size_t ny, size_t nz,
+                                   size_t transitionWidth, size_t borderWidth, int useOuterIfInnerUndefined, void* stream);
+int fimex_amd_border_smooth_host(const float* inner, const float* outerOnInner, float* out, size_t nx, size_t ny, size_t nz,
+                                 size_t transitionWidth, size_t borderWidth, int useOuterIfInnerUndefined);
+/** CDMOverlay::getDataSlice (src/CDMOverlay.cc:82-86) on n values: top where it is defined, else base.  out may be either input
+ *  itself, but must not overlap either otherwise; n == 0 does nothing. */
+int fimex_amd_overlay_device(const float* d_top, const float* d_base, float* d_out, size_t n, void* stream);
+int fimex_amd_overlay_host(const float* top, const float* base, float* out, size_t n);
+
+typedef struct fimex_amd_merge_plan fimex_amd_merge_plan;
+/**
+ * The four steps as one plan.  It borrows three backward plans (nearest, bilinear or bicubic, each with its own method) that the
+ * caller keeps alive as long as the merge plan: outer -> inner grid, (smoothed) inner -> target, outer -> target.  Refused:
+ * transitionWidth == 0, forward plans, plans on different devices, shapes that do not chain (outerToInner.in == outerToTarget.in,
+ * outerToInner.out == innerToTarget.in, innerToTarget.out == outerToTarget.out).
+ */
+int fimex_amd_merge_plan_create(const fimex_amd_regrid_plan* outerToInner, const fimex_amd_regrid_plan* innerToTarget,
+                                const fimex_amd_regrid_plan* outerToTarget, size_t transitionWidth, size_t borderWidth,
+                                int useOuterIfInnerUndefined, fimex_amd_merge_plan** plan);
+int fimex_amd_merge_plan_destroy(fimex_amd_merge_plan* plan);
+/**
+ * CDMMerger::getDataSlice: inner [nz][iy][ix] and outer [nz][oy][ox] -> out [nz][ty][tx], steps 1-4 in two fused kernels that
+ * evaluate the plans cell by cell only where a step reads them.  The smoothed inner field is stream-ordered
+ * scratch.  out must not overlap the inputs; nz == 0 does nothing.  The _device form runs on the plans' device.
+ */
+int fimex_amd_merge_apply_device(const fimex_amd_merge_plan* plan, const float* d_inner, const float* d_outer, size_t nz, float* d_out,
+                                 void* stream);
+int fimex_amd_merge_apply_host(const fimex_amd_merge_plan* plan, const float* inner, const float* outer, size_t nz, float* out);
+/** The same result by fimex_amd_regrid_apply_device three times and the two elementwise kernels, on temporaries: the cross-check
+ *  and the yardstick of the fused kernels (as fimex_amd_regrid_apply_gather_device is for the staged ones). */
+int fimex_amd_merge_apply_chain_device(const fimex_amd_merge_plan* plan, const float* d_inner, const float* d_outer, size_t nz, float* d_out,
+                                       void* stream);
+
 /* ----------------------------------- plan building across projections (8f n2) */
 /* The reference calls PROJ.4 (pj_init_plus / pj_transform) here; this library carries its own projections:
  * latlong/longlat, stere, lcc, merc, tmerc, etmerc, utm, laea, aea, geos, omerc, sinu, cea, ortho, aeqd, nsper, ob_tran with o_proj=longlat (radians at this boundary for
