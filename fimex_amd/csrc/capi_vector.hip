@@ -1,0 +1,324 @@
+// extern "C" boundary, vectors and projections: the vector reprojection plan and its applies (vector.hip), the proj-level entries
+// (projection.hip), the coordinate searches (coordsearch.hip) and points2position (convert.hip).
+#include "host_call.hpp"
+
+#include <memory>
+
+using namespace fimex_amd;
+
+namespace {
+
+template <class Call>
+void points2position(Call&& c, double* points, size_t n, const double* axis, int num, int axis_type)
+{
+    if (n == 0) return;
+    FA_REQUIRE(points != nullptr && axis != nullptr, "NULL argument");
+    (void)current_device_checked();
+    launch_points2position(c.inout(points, n), n, axis, num, axis_type, c.stream());
+    c.finish();
+}
+
+template <class Call>
+void project_values(Call&& c, const char* proj_input, const char* proj_output, double* x, double* y, size_t num, const char* nullArray)
+{
+    FA_REQUIRE(num == 0 || (x != nullptr && y != nullptr), nullArray);
+    (void)current_device_checked();
+    launch_project_values(proj_input, proj_output, c.inout(x, num), c.inout(y, num), num, c.stream());
+    c.finish();
+}
+
+template <class Call>
+void project_axes(Call&& c, const char* proj_input, const char* proj_output, const double* in_x_axis, const double* in_y_axis, size_t ix,
+                  size_t iy, double* outX, double* outY)
+{
+    const size_t n = ix * iy;
+    FA_REQUIRE(n == 0 || (in_x_axis != nullptr && in_y_axis != nullptr && outX != nullptr && outY != nullptr), "NULL argument");
+    (void)current_device_checked();
+    launch_project_axes(proj_input, proj_output, in_x_axis, in_y_axis, ix, iy, c.out(outX, n), c.out(outY, n), c.stream());
+    c.finish();
+}
+
+template <class Call>
+void vector_reproject_matrix(Call&& c, const char* proj_input, const char* proj_output, const double* out_x_axis, const double* out_y_axis,
+                             int xType, int yType, size_t ox, size_t oy, double* matrix)
+{
+    FA_REQUIRE(ox * oy == 0 || (out_x_axis != nullptr && out_y_axis != nullptr && matrix != nullptr), "NULL argument");
+    (void)current_device_checked();
+    launch_vector_reproject_matrix(proj_input, proj_output, out_x_axis, out_y_axis, xType, yType, ox, oy, c.out(matrix, 4 * ox * oy), c.stream());
+    c.finish();
+}
+
+void check_coord_search_host(const double* px, const double* py, size_t nPoints, const double* lon, const double* lat, size_t n)
+{
+    FA_REQUIRE(nPoints == 0 || (px != nullptr && py != nullptr), "NULL argument");
+    FA_REQUIRE(n == 0 || (lon != nullptr && lat != nullptr), "NULL argument");
+}
+
+}  // namespace
+
+extern "C" {
+
+int fimex_amd_vector_plan_create(const double* matrix, size_t ox, size_t oy, fimex_amd_vector_plan** out)
+{
+    return c_guard([&] {
+        FA_REQUIRE(out != nullptr, "plan output pointer is NULL");
+        *out = nullptr;
+        FA_REQUIRE(matrix != nullptr, "matrix is NULL");
+        auto plan = std::make_unique<fimex_amd_vector_plan>();
+        plan->device = current_device_checked();
+        plan->ox = ox;
+        plan->oy = oy;
+        build_vector_plan(*plan, matrix);
+        *out = plan.release();
+    });
+}
+
+int fimex_amd_vector_plan_destroy(fimex_amd_vector_plan* plan)
+{
+    return c_guard([&] {
+        if (!plan) return;
+        ScopedDevice dev(plan->device);
+        delete plan;
+    });
+}
+
+// the vector reprojection pairs differ in their refusals and in their device policy (the host form switches to the plan's
+// device, the device form demands it or, for direction_scaled, switches too): each keeps its own body
+
+int fimex_amd_vector_reproject_values_host(const fimex_amd_vector_plan* plan, float* u, float* v, size_t size)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL plan");
+        const size_t layer = plan->ox * plan->oy;
+        const size_t oz = size / layer;  // CachedVectorReprojection.cc:41
+        if (oz == 0) return;
+        FA_REQUIRE(u != nullptr && v != nullptr, "NULL buffer");
+        ScopedDevice dev(plan->device);
+        HostCall hc;
+        launch_vector_values(*plan, hc.inout(u, oz * layer), hc.inout(v, oz * layer), oz, hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_vector_reproject_values_device(const fimex_amd_vector_plan* plan, float* d_u, float* d_v, size_t oz, void* stream)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL plan");
+        if (oz == 0) return;
+        FA_REQUIRE(d_u != nullptr && d_v != nullptr, "NULL device buffer");
+        require_current_device(plan->device);
+        launch_vector_values(*plan, d_u, d_v, oz, as_stream(stream));
+    });
+}
+
+int fimex_amd_vector_reproject_direction_host(const fimex_amd_vector_plan* plan, float* angles, size_t size)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL plan");
+        const size_t layer = plan->ox * plan->oy;
+        const size_t oz = size / layer;  // CachedVectorReprojection.cc:52
+        if (oz == 0) return;
+        FA_REQUIRE(angles != nullptr, "NULL buffer");
+        ScopedDevice dev(plan->device);
+        HostCall hc;
+        launch_vector_direction(*plan, hc.inout(angles, oz * layer), oz, hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_vector_reproject_direction_device(const fimex_amd_vector_plan* plan, float* d_angles, size_t oz, void* stream)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL plan");
+        if (oz == 0) return;
+        FA_REQUIRE(d_angles != nullptr, "NULL device buffer");
+        require_current_device(plan->device);
+        launch_vector_direction(*plan, d_angles, oz, as_stream(stream));
+    });
+}
+
+int fimex_amd_vector_reproject_direction_scaled_device(const fimex_amd_vector_plan* plan, float* d_angles, size_t oz, double scale,
+                                                       double offset, void* stream)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr && (oz == 0 || d_angles != nullptr), "NULL argument");
+        ScopedDevice dev(plan->device);
+        launch_vector_direction_scaled(*plan, d_angles, oz, scale, offset, as_stream(stream));
+    });
+}
+
+int fimex_amd_vector_reproject_direction_scaled_host(const fimex_amd_vector_plan* plan, float* angles, size_t size, double scale, double offset)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL argument");
+        const size_t layer = plan->ox * plan->oy, oz = layer ? size / layer : 0;
+        if (oz == 0) return;
+        FA_REQUIRE(angles != nullptr, "NULL argument");
+        ScopedDevice dev(plan->device);
+        HostCall hc;
+        launch_vector_direction_scaled(*plan, hc.inout(angles, oz * layer), oz, scale, offset, hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_rotate_vector_typed_host(const fimex_amd_vector_plan* plan, const void* xData, int xType, double xFill, const void* yData,
+                                       int yType, double yFill, size_t size, int returnX, int outType, double outFill, void* outData)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL argument");
+        const size_t ex = cdm_type_size(xType), ey = cdm_type_size(yType), eo = cdm_type_size(outType);
+        const size_t layer = plan->ox * plan->oy, oz = layer ? size / layer : 0;
+        if (size == 0) return;
+        FA_REQUIRE(xData != nullptr && yData != nullptr && outData != nullptr, "NULL argument");
+        ScopedDevice dev(plan->device);
+        DeviceArray<float> d_u(size), d_v(size);  // before hc: released after hc has waited for its stream
+        HostCall hc;
+        hipStream_t st = hc.stream();
+        float *u = d_u.get(), *v = d_v.get();
+        launch_data2interpolation(hc.in_bytes(xData, size * ex), xType, size, xFill, u, st);   // CDMProcessor.cc:607-608
+        launch_data2interpolation(hc.in_bytes(yData, size * ey), yType, size, yFill, v, st);
+        launch_vector_values(*plan, u, v, oz, st);                     // :612 (whole slices only, as the reference)
+        launch_interpolation2data(returnX ? u : v, size, outType, outFill, hc.out_bytes(outData, size * eo), st);  // :614-618
+        hc.finish();
+    });
+}
+
+int fimex_amd_points2position_device(double* d_points, size_t n, const double* axis, int num, int axis_type, void* stream)
+{
+    return c_guard([&] { points2position(DeviceCall{as_stream(stream)}, d_points, n, axis, num, axis_type); });
+}
+
+int fimex_amd_points2position_host(double* points, size_t n, const double* axis, int num, int axis_type)
+{
+    return c_guard([&] { points2position(HostCall(), points, n, axis, num, axis_type); });
+}
+
+int fimex_amd_project_values_device(const char* proj_input, const char* proj_output, double* d_x, double* d_y, size_t num, void* stream)
+{
+    return c_guard([&] { project_values(DeviceCall{as_stream(stream)}, proj_input, proj_output, d_x, d_y, num, "NULL device buffer"); });
+}
+
+int fimex_amd_project_values_host(const char* proj_input, const char* proj_output, double* x, double* y, size_t num)
+{
+    return c_guard([&] { project_values(HostCall(), proj_input, proj_output, x, y, num, "NULL argument"); });
+}
+
+int fimex_amd_project_axes_device(const char* proj_input, const char* proj_output, const double* in_x_axis, const double* in_y_axis,
+                                  size_t ix, size_t iy, double* d_outX, double* d_outY, void* stream)
+{
+    return c_guard([&] { project_axes(DeviceCall{as_stream(stream)}, proj_input, proj_output, in_x_axis, in_y_axis, ix, iy, d_outX, d_outY); });
+}
+
+int fimex_amd_project_axes_host(const char* proj_input, const char* proj_output, const double* in_x_axis, const double* in_y_axis,
+                                size_t ix, size_t iy, double* outX, double* outY)
+{
+    return c_guard([&] { project_axes(HostCall(), proj_input, proj_output, in_x_axis, in_y_axis, ix, iy, outX, outY); });
+}
+
+int fimex_amd_get_vector_reproject_matrix_device(const char* proj_input, const char* proj_output, const double* out_x_axis,
+                                                 const double* out_y_axis, int xType, int yType, size_t ox, size_t oy,
+                                                 double* d_matrix, void* stream)
+{
+    return c_guard([&] {
+        vector_reproject_matrix(DeviceCall{as_stream(stream)}, proj_input, proj_output, out_x_axis, out_y_axis, xType, yType, ox, oy, d_matrix);
+    });
+}
+
+int fimex_amd_get_vector_reproject_matrix_host(const char* proj_input, const char* proj_output, const double* out_x_axis,
+                                               const double* out_y_axis, int xType, int yType, size_t ox, size_t oy, double* matrix)
+{
+    return c_guard([&] { vector_reproject_matrix(HostCall(), proj_input, proj_output, out_x_axis, out_y_axis, xType, yType, ox, oy, matrix); });
+}
+
+int fimex_amd_get_vector_reproject_matrix_field_host(const char* proj_input, const char* proj_output, const double* in_x_field,
+                                                     const double* in_y_field, size_t ox, size_t oy, double* matrix)
+{
+    return c_guard([&] {
+        const size_t n = ox * oy;
+        FA_REQUIRE(n == 0 || (in_x_field != nullptr && in_y_field != nullptr && matrix != nullptr), "NULL argument");
+        (void)current_device_checked();
+        HostCall hc;
+        launch_vector_reproject_matrix_field(proj_input, proj_output, in_x_field, in_y_field, ox, oy, hc.out(matrix, 4 * n), hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_get_vector_reproject_matrix_points_host(const char* proj_input, const char* proj_output, int inputIsMetric,
+                                                      const double* out_x_points, const double* out_y_points, size_t on, double* matrix)
+{
+    return c_guard([&] {
+        FA_REQUIRE(on == 0 || (out_x_points != nullptr && out_y_points != nullptr && matrix != nullptr), "NULL argument");
+        (void)current_device_checked();
+        HostCall hc;
+        launch_vector_reproject_matrix_points(proj_input, proj_output, inputIsMetric, out_x_points, out_y_points, on, hc.out(matrix, 4 * on),
+                                              hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_projection_is_degree(const char* proj)
+{
+    int r = -1;
+    const int rc = c_guard([&] { r = projection_is_degree(proj); });
+    return rc == FIMEX_AMD_OK ? r : -1;
+}
+
+// the coordinate searches refuse differently in their two forms: each keeps its own body
+
+int fimex_amd_coord_nearest_host(double* px, double* py, size_t nPoints, const double* lon, const double* lat, size_t orgX, size_t orgY)
+{
+    return c_guard([&] {
+        const size_t n = orgX * orgY;
+        check_coord_search_host(px, py, nPoints, lon, lat, n);
+        (void)current_device_checked();
+        HostCall hc;
+        launch_coord_nearest(hc.inout(px, nPoints), hc.inout(py, nPoints), nPoints, hc.in(lon, n), hc.in(lat, n), orgX, orgY, hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_coord_nearest_device(double* d_px, double* d_py, size_t nPoints, const double* d_lon, const double* d_lat, size_t orgX, size_t orgY,
+                                   void* stream)
+{
+    return c_guard([&] {
+        FA_REQUIRE(nPoints == 0 || (d_px != nullptr && d_py != nullptr && d_lon != nullptr && d_lat != nullptr), "NULL device buffer");
+        (void)current_device_checked();
+        launch_coord_nearest(d_px, d_py, nPoints, d_lon, d_lat, orgX, orgY, as_stream(stream));
+    });
+}
+
+int fimex_amd_coord_kdtree_host(double maxDist, double* px, double* py, size_t nPoints, const double* lon, const double* lat, size_t orgX, size_t orgY)
+{
+    return c_guard([&] {
+        const size_t n = orgX * orgY;
+        check_coord_search_host(px, py, nPoints, lon, lat, n);
+        (void)current_device_checked();
+        HostCall hc;
+        launch_coord_kdtree(maxDist, hc.inout(px, nPoints), hc.inout(py, nPoints), nPoints, hc.in(lon, n), hc.in(lat, n), orgX, orgY,
+                            hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_coord_kdtree_device(double maxDist, double* d_px, double* d_py, size_t nPoints, const double* d_lon, const double* d_lat, size_t orgX,
+                                  size_t orgY, void* stream)
+{
+    return c_guard([&] {
+        FA_REQUIRE(nPoints == 0 || (d_px != nullptr && d_py != nullptr && d_lon != nullptr && d_lat != nullptr), "NULL device buffer");
+        (void)current_device_checked();
+        launch_coord_kdtree(maxDist, d_px, d_py, nPoints, d_lon, d_lat, orgX, orgY, as_stream(stream));
+    });
+}
+
+int fimex_amd_grid_distance_host(const double* lon, const double* lat, size_t orgX, size_t orgY, double* maxGridDistance)
+{
+    return c_guard([&] {
+        const size_t n = orgX * orgY;
+        FA_REQUIRE(n > 0 && lon != nullptr && lat != nullptr && maxGridDistance != nullptr, "NULL or empty argument");
+        (void)current_device_checked();
+        HostCall hc;
+        *maxGridDistance = grid_distance(hc.in(lon, n), hc.in(lat, n), orgX, orgY, hc.stream());  // waits for its result: nothing to copy back
+    });
+}
+
+}  // extern "C"

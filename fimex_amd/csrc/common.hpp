@@ -100,6 +100,15 @@ private:
     hipStream_t s_ = nullptr;
 };
 
+// hipEvent_t destroyed on scope exit
+struct __attribute__((visibility("hidden"))) ScopedEvent {
+    hipEvent_t e = nullptr;
+    ScopedEvent() { FA_HIP(hipEventCreate(&e)); }
+    ~ScopedEvent() { (void)hipEventDestroy(e); }
+    ScopedEvent(const ScopedEvent&) = delete;
+    ScopedEvent& operator=(const ScopedEvent&) = delete;
+};
+
 // switches the calling thread to `device` for one call and back afterwards
 class ScopedDevice {
 public:

@@ -271,7 +271,8 @@ void host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st
 void device_to_host(void* h_dst, const void* d_src, size_t bytes, hipStream_t stream);
 void release_host_pipes();
 
-// tuning knobs read once from the environment (FIMEX_AMD_<NAME>), for bench sweeps
+// experiment switches: the measured default in the product library; the tuning build (-DFIMEX_AMD_TUNING) reads FIMEX_AMD_<NAME>
+// from the environment at every call, so that one process can sweep settings (capi.hip)
 int tuning(const char* name, int fallback);
 
 // batches shorter than this take the gather kernels: the staged kernels pay a per-tile set-up (chunk list, per-output plan)
