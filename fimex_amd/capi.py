@@ -414,6 +414,9 @@ class VectorPlan:
         _check(load().fimex_amd_vector_reproject_direction_scaled_host(self._h, _fp(a.reshape(-1)), a.size, scale, offset))
         return a
 
+    def reproject_direction_scaled_device(self, d_angles, oz, scale, offset, stream=0):
+        _check(load().fimex_amd_vector_reproject_direction_scaled_device(self._h, d_angles, oz, scale, offset, stream))
+
 
 def fill2d_process(relaxCrit, corrEff, maxLoop):
     return Process2d(PROCESS_FILL2D, relaxCrit, corrEff, maxLoop, 0, b"\0", 0.0)

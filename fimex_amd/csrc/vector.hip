@@ -171,6 +171,8 @@ VecArgs make_args(const fimex_amd_vector_plan& plan, float* u, float* v, size_t 
     if (chunks > oz) chunks = oz;
     if (chunks < 1) chunks = 1;
     a.zPerBlock = (uint32_t)ceil_div(oz, chunks);
+    const size_t forced = (size_t)tuning("VECTOR_ZPB", 0);  // 0: the rule above; the tests force the multi-slice loops at small layers
+    if (forced != 0) a.zPerBlock = (uint32_t)(forced < oz ? forced : oz);
     chunks = ceil_div(oz, (size_t)a.zPerBlock);
     FA_REQUIRE(chunks <= 65535, "too many z chunks for one launch");
     grid = dim3((uint32_t)blocksX, (uint32_t)chunks, 1);

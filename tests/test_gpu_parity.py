@@ -54,7 +54,9 @@ def test_backward_methods_match_oracle(fa, method, shape):
 @pytest.mark.parametrize("method", [oracle.NEAREST, oracle.BILINEAR, oracle.BICUBIC])
 @pytest.mark.parametrize("nz", [1, 2, 7, 8, 9, 16, 17, 41, 83])
 def test_backward_ragged_z_counts(fa, method, nz):
-    """z counts around the in-kernel unroll factors and the z-chunking of the grid."""
+    """Slice counts around the staged path's threshold (STAGED_MIN_NZ) and the one-slice kernels (apply_few), through whichever
+    kernel apply_host chooses.  The target has 36 tiles, so the gather kernels' launch rule gives one slice per workgroup for every
+    nz here: their unrolled multi-slice loops do not run in this test.  tests/test_gpu_z_chunks.py covers those."""
     inX, inY, outX, outY = 120, 90, 100, 70
     px, py = cases.backward_positions(inX, inY, outX, outY, seed=5)
     f = cases.field(nz, inY, inX, seed=nz)
