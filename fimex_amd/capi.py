@@ -148,6 +148,12 @@ SYMBOLS = {
     "fimex_amd_vertical_velocity_host": (ctypes.c_int, [_Z, _Z, _Z, _Z, ctypes.c_double, ctypes.c_double, _F, _F, _D, _D, _F, _F, _F, _F, _F, _F]),
     "fimex_amd_omega_to_vertical_wind_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V, _V, _V]),
     "fimex_amd_omega_to_vertical_wind_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F, _F, _F]),
+    "fimex_amd_convert_scaled_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                       ctypes.c_double, ctypes.c_double, ctypes.c_double, _V, _V]),
+    "fimex_amd_theta_to_temperature_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, ctypes.c_float, _V, _V]),
+    "fimex_amd_specific_to_relative_humidity_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V, _V, _V]),
+    "fimex_amd_accumulate_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _Z, _Z, _V, _V, _V]),
+    "fimex_amd_deaccumulate_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _Z, _Z, _V, _V, _V]),
     "fimex_amd_border_smooth_device": (ctypes.c_int, [_V, _V, _V, _Z, _Z, _Z, _Z, _Z, ctypes.c_int, _V]),
     "fimex_amd_border_smooth_host": (ctypes.c_int, [_F, _F, _F, _Z, _Z, _Z, _Z, _Z, ctypes.c_int]),
     "fimex_amd_overlay_device": (ctypes.c_int, [_V, _V, _V, _Z, _V]),
@@ -178,6 +184,16 @@ SYMBOLS = {
     "fimex_amd_scan_sum_device": (ctypes.c_int, [_V, _Z, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(ctypes.c_double), _ZP, _V]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_derived_host.h declares: the *_host forms of the (8f n9) entries
+DERIVED_HOST_SYMBOLS = {
+    "fimex_amd_convert_scaled_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
+                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, _V]),
+    "fimex_amd_theta_to_temperature_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F, ctypes.c_float, _F]),
+    "fimex_amd_specific_to_relative_humidity_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F, _F, _V]),
+    "fimex_amd_accumulate_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, _Z, _Z, _D, _D]),
+    "fimex_amd_deaccumulate_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, _Z, _Z, _V, _D]),
+}
+
 _lib = None
 _libs = {}
 
@@ -192,7 +208,7 @@ def _open(path):
     except Exception:
         pass
     lib = ctypes.CDLL(path)
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -777,6 +793,77 @@ def omega_to_vertical_wind_host(pressure, nx, ny, nt, omega, t):
 def omega_to_vertical_wind_device(pressure, nx, ny, nt, d_omega, d_t, d_w, stream=0):
     """The same on device pointers; d_w may be d_omega (in place).  Only enqueues on `stream`."""
     _check(load().fimex_amd_omega_to_vertical_wind_device(_levels_ref(pressure), nx, ny, nt, d_omega, d_t, d_w, stream))
+
+
+def convert_scaled_host(data, oldFill, oldScale, oldOffset, outType, newFill, newScale=1.0, newOffset=0.0):
+    """DataImpl::convertDataType on a host array of a stored type: the array of outType, same shape."""
+    a = np.ascontiguousarray(data)
+    out = np.empty(a.shape, CDM_DTYPES[outType])
+    _check(load().fimex_amd_convert_scaled_host(a.ctypes.data, cdm_type_of(a.dtype), a.size, oldFill, oldScale, oldOffset, outType, newFill,
+                                                newScale, newOffset, out.ctypes.data))
+    return out
+
+
+def convert_scaled_device(d_in, inType, n, oldFill, oldScale, oldOffset, outType, newFill, newScale, newOffset, d_out, stream=0):
+    """The same on device pointers; d_out may be d_in when both types have one size.  Only enqueues on `stream`."""
+    _check(load().fimex_amd_convert_scaled_device(d_in, inType, n, oldFill, oldScale, oldOffset, outType, newFill, newScale, newOffset, d_out,
+                                                  stream))
+
+
+def theta_to_temperature_host(pressure, nx, ny, nt, theta, addOffset=0.0):
+    """ThetaTemperatureConverter (theta2T) on host arrays: float32 [nt][nz][ny][nx], pressure levels in hPa."""
+    ta, tp = _opt(_f32, _fp, theta)
+    out = np.empty((nt, pressure.nz, ny, nx), np.float32)
+    _check(load().fimex_amd_theta_to_temperature_host(_levels_ref(pressure), nx, ny, nt, tp, addOffset, _fp(out.reshape(-1))))
+    return out
+
+
+def theta_to_temperature_device(pressure, nx, ny, nt, d_theta, addOffset, d_T, stream=0):
+    """The same on device pointers; d_T may be d_theta (in place).  Only enqueues on `stream`."""
+    _check(load().fimex_amd_theta_to_temperature_device(_levels_ref(pressure), nx, ny, nt, d_theta, addOffset, d_T, stream))
+
+
+def specific_to_relative_humidity_host(pressure, nx, ny, nt, q, T):
+    """HumidityConverter (specific2relative) on host arrays: q and T float32 [nt][nz][ny][nx] -> int16 with scale factor 1 / 25000."""
+    qa, qp = _opt(_f32, _fp, q)
+    ta, tp = _opt(_f32, _fp, T)
+    out = np.empty((nt, pressure.nz, ny, nx), np.int16)
+    _check(load().fimex_amd_specific_to_relative_humidity_host(_levels_ref(pressure), nx, ny, nt, qp, tp, out.ctypes.data))
+    return out
+
+
+def specific_to_relative_humidity_device(pressure, nx, ny, nt, d_q, d_T, d_rh, stream=0):
+    _check(load().fimex_amd_specific_to_relative_humidity_device(_levels_ref(pressure), nx, ny, nt, d_q, d_T, d_rh, stream))
+
+
+def accumulate_host(data, firstPos=0, prev=None):
+    """CDMProcessor's accumulate over the positions data[0 .. nt-1] = firstPos ..: float64, same shape.  prev: acc[firstPos - 1]."""
+    a = np.ascontiguousarray(data)
+    nt = a.shape[0]
+    p = _f64(prev).reshape(-1) if prev is not None else None
+    out = np.empty(a.shape, np.float64)
+    _check(load().fimex_amd_accumulate_host(a.ctypes.data, cdm_type_of(a.dtype), a.size // nt if nt else 0, nt, firstPos,
+                                            _dp(p) if p is not None else None, _dp(out.reshape(-1))))
+    return out
+
+
+def accumulate_device(d_in, cdmType, n, nt, firstPos, d_prev, d_out, stream=0):
+    _check(load().fimex_amd_accumulate_device(d_in, cdmType, n, nt, firstPos, d_prev, d_out, stream))
+
+
+def deaccumulate_host(data, firstPos=0, prev=None):
+    """CDMProcessor's deaccumulate: float64, same shape.  prev: the position in front of the batch, in the type of data."""
+    a = np.ascontiguousarray(data)
+    nt = a.shape[0]
+    p = np.ascontiguousarray(prev, a.dtype).reshape(-1) if prev is not None else None
+    out = np.empty(a.shape, np.float64)
+    _check(load().fimex_amd_deaccumulate_host(a.ctypes.data, cdm_type_of(a.dtype), a.size // nt if nt else 0, nt, firstPos,
+                                              p.ctypes.data if p is not None else None, _dp(out.reshape(-1))))
+    return out
+
+
+def deaccumulate_device(d_in, cdmType, n, nt, firstPos, d_prev, d_out, stream=0):
+    _check(load().fimex_amd_deaccumulate_device(d_in, cdmType, n, nt, firstPos, d_prev, d_out, stream))
 
 
 def border_smooth_host(inner, outerOnInner, transitionWidth=5, borderWidth=2, useOuterIfInnerUndefined=True):

@@ -7,20 +7,6 @@ using namespace fimex_amd;
 
 namespace {
 
-// a level description for the launch: the caller's own for a device call, with device copies of its 2-D / 3-D members for a
-// host call
-fimex_amd_vertical_levels levels_on(const DeviceCall&, const fimex_amd_vertical_levels& l, size_t, size_t) { return l; }
-
-fimex_amd_vertical_levels levels_on(HostCall& hc, const fimex_amd_vertical_levels& h, size_t plane, size_t nt)
-{
-    fimex_amd_vertical_levels d = h;
-    d.ps = nullptr;
-    d.field = nullptr;
-    if (h.kind == FIMEX_AMD_VLEVEL_FIELD) d.field = hc.in(h.field, nt * h.nz * plane);
-    else if (h.kind != FIMEX_AMD_VLEVEL_AXIS) d.ps = hc.in(h.ps, nt * plane);
-    return d;
-}
-
 // ---- vertical interpolation
 
 // everything fimex_amd_vertical_interpolate_* refuses before any work is queued; returns false when there is nothing to do

@@ -194,6 +194,41 @@ void launch_interpolation2data(const float* d_in, size_t n, int cdmType, double 
 bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                         hipStream_t stream);
 
+// f(T{}) with the C++ type of a numeric fimex_amd_datatype (char is signed on the reference's platforms); throws as cdm_type_size
+template <class F>
+void for_cdm_type(int cdmType, F&& f)
+{
+    switch (cdmType) {
+    case FIMEX_AMD_CDM_CHAR: f((signed char)0); break;
+    case FIMEX_AMD_CDM_SHORT: f((short)0); break;
+    case FIMEX_AMD_CDM_INT: f((int)0); break;
+    case FIMEX_AMD_CDM_FLOAT: f((float)0); break;
+    case FIMEX_AMD_CDM_DOUBLE: f((double)0); break;
+    case FIMEX_AMD_CDM_UCHAR: f((unsigned char)0); break;
+    case FIMEX_AMD_CDM_USHORT: f((unsigned short)0); break;
+    case FIMEX_AMD_CDM_UINT: f((unsigned int)0); break;
+    case FIMEX_AMD_CDM_INT64: f((long long)0); break;
+    case FIMEX_AMD_CDM_UINT64: f((unsigned long long)0); break;
+    default: (void)cdm_type_size(cdmType);
+    }
+}
+
+// scaled_convert.hip: ScaleValue<IN, OUT> between stored types
+bool scaled_fill_representable(int cdmType, double fill);  // static_cast<T>(fill) is defined
+void launch_convert_scaled(const void* d_in, int inType, size_t n, double oldFill, double oldScale, double oldOffset, int outType, double newFill,
+                           double newScale, double newOffset, void* d_out, hipStream_t stream);
+
+// pressure_convert.hip: theta2T and specific2relative of CDMPressureConversions on a level description
+void launch_theta_to_temperature(const fimex_amd_vertical_levels& pressure, size_t nx, size_t ny, size_t nt, const float* d_theta, float addOffset,
+                                 float* d_T, hipStream_t stream);
+void launch_specific_to_relative_humidity(const fimex_amd_vertical_levels& pressure, size_t nx, size_t ny, size_t nt, const float* d_q,
+                                          const float* d_T, short* d_rh, hipStream_t stream);
+
+// time_accumulate.hip: accumulate / deAccumulate of CDMProcessor along the unlimited dimension
+void launch_accumulate(const void* d_in, int cdmType, size_t n, size_t nt, size_t firstPos, const double* d_prev, double* d_out, hipStream_t stream);
+void launch_deaccumulate(const void* d_in, int cdmType, size_t n, size_t nt, size_t firstPos, const void* d_prev, double* d_out,
+                         hipStream_t stream);
+
 // vertical.hip: vertical interpolation to fixed or template levels
 bool vertical_method_known(int method);
 void check_vertical_levels(const fimex_amd_vertical_levels* levels, const char* which, bool nonEmpty);  // throws: unknown kind, missing array

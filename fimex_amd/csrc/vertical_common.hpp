@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <type_traits>
 
 namespace fimex_amd {
 
@@ -122,6 +123,19 @@ Levels device_levels(const fimex_amd_vertical_levels& l, StreamScratch& scratch,
         d.c1 = c1;
     }
     return d;
+}
+
+// kind is a compile-time constant in the kernels that take it as a template argument: f(std::integral_constant<int, kind>)
+template <class F>
+void for_level_kind(int kind, F&& f)
+{
+    switch (kind) {
+    case FIMEX_AMD_VLEVEL_FIELD: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_FIELD>{}); break;
+    case FIMEX_AMD_VLEVEL_AXIS: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_AXIS>{}); break;
+    case FIMEX_AMD_VLEVEL_SIGMA: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_SIGMA>{}); break;
+    case FIMEX_AMD_VLEVEL_HYBRID_SIGMA: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_HYBRID_SIGMA>{}); break;
+    default: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_HYBRID_SIGMA_AP>{}); break;
+    }
 }
 
 dim3 column_grid(size_t plane, size_t nt)

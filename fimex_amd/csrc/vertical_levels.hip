@@ -36,19 +36,6 @@ struct AltitudeArgs {
     int surfaceFirst;    // 1, 0 or FIMEX_AMD_VORDER_AUTO
 };
 
-// kind is a compile-time constant in the kernels below: f(std::integral_constant<int, kind>)
-template <class F>
-void for_level_kind(int kind, F&& f)
-{
-    switch (kind) {
-    case FIMEX_AMD_VLEVEL_FIELD: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_FIELD>{}); break;
-    case FIMEX_AMD_VLEVEL_AXIS: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_AXIS>{}); break;
-    case FIMEX_AMD_VLEVEL_SIGMA: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_SIGMA>{}); break;
-    case FIMEX_AMD_VLEVEL_HYBRID_SIGMA: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_HYBRID_SIGMA>{}); break;
-    default: f(std::integral_constant<int, FIMEX_AMD_VLEVEL_HYBRID_SIGMA_AP>{}); break;
-    }
-}
-
 // U levels of one column, i0 .. i0 + U - 1 counted from the surface: the body of the loop of :190-207
 template <int U, bool kHumidity>
 __device__ __forceinline__ void integrate_levels(const Column& col, const float* Tcol, const float* qcol, float* res, unsigned i0, unsigned nz,

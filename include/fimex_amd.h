@@ -621,6 +621,84 @@ int fimex_amd_merge_apply_host(const fimex_amd_merge_plan* plan, const float* in
 int fimex_amd_merge_apply_chain_device(const fimex_amd_merge_plan* plan, const float* d_inner, const float* d_outer, size_t nz, float* d_out,
                                        void* stream);
 
+/* ------------- scaled reads and writes, theta2T, humidity, accumulate (8f n9) */
+/* The arithmetic around the entries above that the reference keeps in its readers and decorators: unpacking stored data
+ * (scale_factor, add_offset, _FillValue, a linear unit change) into the floats n5-n8 take, packing results for the writers, the
+ * theta2T and specific2relative converters of CDMPressureConversions, and accumulate / deAccumulate of CDMProcessor.  The
+ * entries declared here only enqueue work on the stream and never synchronise it (the coefficient arrays of a level description
+ * are host arrays, as everywhere).  Their *_host forms, on host buffers, are declared in fimex_amd_derived_host.h. */
+
+/**
+ * DataImpl<IN>::convertDataType -> ScaleValue<IN, OUT> (include/fimex/Utils.h:443-464, src/DataImpl.h:316-349) on n elements,
+ * for every pair of the ten numeric fimex_amd_datatype values (NAT and STRING return -1).  With a = oldScale / newScale and
+ * b = (oldOffset - newOffset) / newScale, taken once in double: an element equal to (IN)oldFill, or NaN for a floating IN, gives
+ * (OUT)newFill; any other gives data_caster<OUT, double>(a * in + b) with the product and the sum in double: for an integer OUT
+ * static_cast<OUT>((int)lround(.)), half away from zero, with the int's wrap-around (and 0 beyond the range of long, DESIGN.md
+ * divergence D6), for float and double a plain cast.
+ *
+ * getScaledDataSliceInUnit(var, unit, t) maps onto it as CDMReader::scaleDataOf (src/CDMReader.cc:164-179) does, a linear unit
+ * change (unitScale, unitOffset: new = unitScale * old + unitOffset) folded into the arguments:
+ *   oldFill = _FillValue, oldScale = scale_factor * unitScale, oldOffset = unitScale * add_offset + unitOffset,
+ *   outType = FIMEX_AMD_CDM_DOUBLE, newFill = NaN, newScale = 1, newOffset = 0.
+ * outType FIMEX_AMD_CDM_FLOAT gives what ->asFloat() of that slice holds (the input of every n5-n8 entry), bit for bit: the same
+ * double rounded to float once.  Non-linear unit conversions (ScaleValueUnits) are not covered.
+ * The writers' packing is the same call with the variable's own fill, scale and offset as the new* arguments.
+ *
+ * Two divergences.  Where static_cast<IN>(oldFill) is undefined in the reference (a NaN or a value beyond the range of an integer
+ * IN, a finite value beyond the range of float) the data has no fill value here: no element compares equal.  A newFill that OUT
+ * cannot hold in the same sense returns -1.
+ * out may be in itself when both types have the same size; any other overlap returns -1.  n == 0 does nothing.
+ * Throughput depends on the two pointers: 16-byte accesses need a common element offset below 16 at which both are 16-byte
+ * aligned (always so for two 16-byte aligned buffers, or two buffers shifted by the same number of elements); otherwise every
+ * element goes on its own, which is correct and slower.
+ */
+int fimex_amd_convert_scaled_device(const void* d_in, int inType, size_t n, double oldFill, double oldScale, double oldOffset, int outType,
+                                    double newFill, double newScale, double newOffset, void* d_out, void* stream);
+
+/**
+ * ThetaTemperatureConverter::getDataSlice (src/CDMPressureConversions.cc:226-245), all in float:
+ * T = ((theta + addOffset) * powf(p * (1 / 1000.f), Rcp)) - addOffset, Rcp = (float)(8.31432 / 0.0289644) / 1004.f, p the level's
+ * pressure as float in hPa (what fimex_amd_vertical_levels_* would write; a formula kind is evaluated per column, no pressure field
+ * is needed), addOffset the add_offset attribute of theta.  theta and T [nt][pressure->nz][ny][nx]; T may be theta itself (the
+ * reference converts in place) but must not overlap anything else.  The device's powf is not the host's: T is within
+ * 3 * 2^-23 * |(theta + addOffset) * powf(.)| of the reference's.
+ */
+int fimex_amd_theta_to_temperature_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* d_theta,
+                                          float addOffset, float* d_T, void* stream);
+
+/**
+ * HumidityConverter::getDataSlice (src/CDMPressureConversions.cc:313-333): relative humidity packed as short with scale factor
+ * 1 / 25000 from specific humidity q (1), air temperature T (K) and the level's pressure p as float in hPa, by
+ * mifi_specific_to_relative_humidity (src/vertical_coordinate_transformations.c:114-141):
+ *   es = (float)(610.78f * exp((17.269f * (T - 273.16f)) / (T - 35.86f)))   the argument in float, exp and the product in double
+ *   rh = (float)(100. * q * p / (es * 0.622))                               in double, then clamped to [0, 100] (NaN stays)
+ *   packed = (short)(25000.f * rh + 0.5)                                    a float product, + 0.5 in double, truncation
+ * Where a short cannot hold the result the reference is undefined; written here is what its x86-64 build yields: the value
+ * truncated to int32, of which the low 16 bits are kept (rh = 1.4 gives -30536, rh = 3 gives 9464), and 0 for NaN.
+ * q, T and rh [nt][pressure->nz][ny][nx]; rh must not overlap an input.  The device's exp is not the host's: an element differs
+ * from the reference's by at most one count, and almost none does.
+ */
+int fimex_amd_specific_to_relative_humidity_device(const fimex_amd_vertical_levels* pressure, size_t nx, size_t ny, size_t nt, const float* d_q,
+                                                   const float* d_T, short* d_rh, void* stream);
+
+/**
+ * The accumulation of CDMProcessor::getDataSlice (src/CDMProcessor.cc:470-491, :534-558) for nt positions of the unlimited
+ * dimension, firstPos .. firstPos + nt - 1: in [nt][n] elements of cdmType, read as Data::asDouble() (a cast, no fill value
+ * handling), out double[nt][n].  In the order a writer pulling positions 0, 1, 2, ... gets from the reference's slice cache:
+ *   acc[0] = in[0] (its NaN kept), acc[1] = in[1] + nan0(in[0]), acc[t] = in[t] + acc[t-1]
+ * where nan0 replaces NaN by 0 and applies to position 0 only, where it is the addend.  prev: double[n] holding acc[firstPos - 1],
+ * required when firstPos > 0 and ignored otherwise (for firstPos == 1 it is position 0 and gets nan0).  Bit for bit.
+ * out must not overlap in or prev; n == 0 or nt == 0 does nothing.
+ */
+int fimex_amd_accumulate_device(const void* d_in, int cdmType, size_t n, size_t nt, size_t firstPos, const double* d_prev, double* d_out,
+                                void* stream);
+/**
+ * The deaccumulation (:560-578): out[0] = in[0], out[t] = in[t] - in[t-1] with nan0 on in[0] where it is the subtrahend.
+ * prev: in[firstPos - 1], n elements of cdmType, required when firstPos > 0.  Everything else as above.
+ */
+int fimex_amd_deaccumulate_device(const void* d_in, int cdmType, size_t n, size_t nt, size_t firstPos, const void* d_prev, double* d_out,
+                                  void* stream);
+
 /* ----------------------------------- plan building across projections (8f n2) */
 /* The reference calls PROJ.4 (pj_init_plus / pj_transform) here; this library carries its own projections:
  * latlong/longlat, stere, lcc, merc, tmerc, etmerc, utm, laea, aea, geos, omerc, sinu, cea, ortho, aeqd, nsper, ob_tran with o_proj=longlat (radians at this boundary for
