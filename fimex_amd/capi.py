@@ -154,6 +154,10 @@ SYMBOLS = {
     "fimex_amd_specific_to_relative_humidity_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V, _V, _V]),
     "fimex_amd_accumulate_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _Z, _Z, _V, _V, _V]),
     "fimex_amd_deaccumulate_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _Z, _Z, _V, _V, _V]),
+    "fimex_amd_time_mapping": (ctypes.c_int, [_D, _Z, _D, _Z, _ZP, _ZP]),
+    "fimex_amd_time_interpolate_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _D, _Z, _D, _Z, _V, _V]),
+    "fimex_amd_quality_mask_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _V, ctypes.c_int, _Z, ctypes.c_int, _D, _Z, ctypes.c_double,
+                                                     ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _V]),
     "fimex_amd_border_smooth_device": (ctypes.c_int, [_V, _V, _V, _Z, _Z, _Z, _Z, _Z, ctypes.c_int, _V]),
     "fimex_amd_border_smooth_host": (ctypes.c_int, [_F, _F, _F, _Z, _Z, _Z, _Z, _Z, ctypes.c_int]),
     "fimex_amd_overlay_device": (ctypes.c_int, [_V, _V, _V, _Z, _V]),
@@ -194,6 +198,13 @@ DERIVED_HOST_SYMBOLS = {
     "fimex_amd_deaccumulate_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, _Z, _Z, _V, _D]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_time_quality_host.h declares: the *_host forms of the (8f n10) entries
+TIME_QUALITY_HOST_SYMBOLS = {
+    "fimex_amd_time_interpolate_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, _D, _Z, _D, _Z, _F]),
+    "fimex_amd_quality_mask_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, _V, ctypes.c_int, _Z, ctypes.c_int, _D, _Z, ctypes.c_double,
+                                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+}
+
 _lib = None
 _libs = {}
 
@@ -208,7 +219,7 @@ def _open(path):
     except Exception:
         pass
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -864,6 +875,60 @@ def deaccumulate_host(data, firstPos=0, prev=None):
 
 def deaccumulate_device(d_in, cdmType, n, nt, firstPos, d_prev, d_out, stream=0):
     _check(load().fimex_amd_deaccumulate_device(d_in, cdmType, n, nt, firstPos, d_prev, d_out, stream))
+
+
+# fimex_amd_time_interpolate_device: output steps per launch, and per chunk where a launch is split over gridDim.y (include/fimex_amd.h)
+TIME_LAUNCH_STEPS, TIME_CHUNK_STEPS = 128, 32
+
+
+def time_mapping(oldTimes, newTimes):
+    """The slice mapping of CDMTimeInterpolator::changeTimeAxis: (t1, t2), two index arrays of len(newTimes).  Runs on the CPU."""
+    o, x = _f64(oldTimes).reshape(-1), _f64(newTimes).reshape(-1)
+    t1, t2 = np.zeros(x.size, np.uintp), np.zeros(x.size, np.uintp)
+    _check(load().fimex_amd_time_mapping(_dp(o), o.size, _dp(x), x.size, t1.ctypes.data_as(_ZP), t2.ctypes.data_as(_ZP)))
+    return t1, t2
+
+
+def time_interpolate_host(data, oldTimes, newTimes):
+    """CDMTimeInterpolator on a host array of a stored type, data[nOld, ...]: float32 [nNew, ...]."""
+    a = np.ascontiguousarray(data)
+    o, x = _f64(oldTimes).reshape(-1), _f64(newTimes).reshape(-1)
+    if a.shape[0] != o.size:
+        raise ValueError("data holds %d slices for %d old times" % (a.shape[0], o.size))
+    out = np.empty((x.size,) + a.shape[1:], np.float32)
+    _check(load().fimex_amd_time_interpolate_host(a.ctypes.data, cdm_type_of(a.dtype), a.size // o.size if o.size else 0, _dp(o), o.size, _dp(x),
+                                                  x.size, _fp(out.reshape(-1))))
+    return out
+
+
+def time_interpolate_device(d_in, cdmType, n, oldTimes, newTimes, d_out, stream=0):
+    """The same on device pointers: d_in [nOld][n] of cdmType, d_out float32 [nNew][n].  Only enqueues on `stream`."""
+    o, x = _f64(oldTimes).reshape(-1), _f64(newTimes).reshape(-1)
+    _check(load().fimex_amd_time_interpolate_device(d_in, cdmType, n, _dp(o), o.size, _dp(x), x.size, d_out, stream))
+
+
+# fimex_amd_quality_mode
+QUALITY_VALUES, QUALITY_ALL, QUALITY_MAX, QUALITY_MIN, QUALITY_HIGHEST, QUALITY_LOWEST = 0, 1, 2, 3, 4, 5
+_NAN = float("nan")
+
+
+def quality_mask_host(data, status, mode, fillValue, values=(), limit=_NAN, validMin=_NAN, validMax=_NAN, statusFill=_NAN):
+    """CDMQualityExtractor on host arrays of stored types: a masked copy of data.  status=None: the data is its own status.
+    Sizes the library refuses raise; the reference's warn-and-pass-on is the caller's part."""
+    out = np.array(data, order="C", copy=True)
+    s = out if status is None else np.ascontiguousarray(status)
+    v = _f64(values).reshape(-1)
+    _check(load().fimex_amd_quality_mask_host(out.ctypes.data, cdm_type_of(out.dtype), out.size, s.ctypes.data, cdm_type_of(s.dtype), s.size, mode,
+                                              _dp(v) if v.size else None, v.size, limit, validMin, validMax, statusFill, fillValue))
+    return out
+
+
+def quality_mask_device(d_data, dataType, nData, d_status, statusType, nStatus, mode, fillValue, values=(), limit=_NAN, validMin=_NAN,
+                        validMax=_NAN, statusFill=_NAN, stream=0):
+    """The same in place on device pointers; d_status may be d_data (one type, one size).  Only enqueues on `stream`."""
+    v = _f64(values).reshape(-1)
+    _check(load().fimex_amd_quality_mask_device(d_data, dataType, nData, d_status, statusType, nStatus, mode, _dp(v) if v.size else None, v.size,
+                                                limit, validMin, validMax, statusFill, fillValue, stream))
 
 
 def border_smooth_host(inner, outerOnInner, transitionWidth=5, borderWidth=2, useOuterIfInnerUndefined=True):

@@ -229,6 +229,27 @@ void launch_accumulate(const void* d_in, int cdmType, size_t n, size_t nt, size_
 void launch_deaccumulate(const void* d_in, int cdmType, size_t n, size_t nt, size_t firstPos, const void* d_prev, double* d_out,
                          hipStream_t stream);
 
+// time_interpolate.hip: a series onto a new time axis (CDMTimeInterpolator); one entry per output step, worked out on the host
+enum class TimeStepClass : unsigned char { CopyA = 0, CopyB = 1, Blend = 2, Undefined = 3 };
+struct TimeStep {
+    uint32_t t1, t2;  // the pair of input slices
+    float f;          // the blend factor of interpolation.c:1087
+    TimeStepClass cls;
+};
+void launch_time_interpolate(const void* d_in, int cdmType, size_t n, const TimeStep* h_steps, size_t nNew, float* d_out, hipStream_t stream);
+
+// quality.hip: the status rules of CDMQualityExtractor, in place on the data
+struct QualityRule {
+    int mode;  // fimex_amd_quality_mode
+    double limit, validMin, validMax, statusFill;
+    const double* h_values;  // VALUES: sorted, without NaN
+    size_t nValues;
+};
+bool quality_mode_known(int mode);
+bool quality_fill_representable(int cdmType, double fill);  // data_caster<C, double>(fill) gives the rounded fill back
+void launch_quality_mask(void* d_data, int dataType, size_t nData, const void* d_status, int statusType, size_t nStatus, const QualityRule& rule,
+                         double fillValue, hipStream_t stream);
+
 // vertical.hip: vertical interpolation to fixed or template levels
 bool vertical_method_known(int method);
 void check_vertical_levels(const fimex_amd_vertical_levels* levels, const char* which, bool nonEmpty);  // throws: unknown kind, missing array

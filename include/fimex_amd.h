@@ -699,6 +699,71 @@ int fimex_amd_accumulate_device(const void* d_in, int cdmType, size_t n, size_t 
 int fimex_amd_deaccumulate_device(const void* d_in, int cdmType, size_t n, size_t nt, size_t firstPos, const void* d_prev, double* d_out,
                                   void* stream);
 
+/* ------------------------------------------- time axis and quality mask (8f n10) */
+/* The *_host forms of the two *_device entries below are declared in fimex_amd_time_quality_host.h. */
+
+/**
+ * The slice mapping of CDMTimeInterpolator::changeTimeAxis (src/CDMTimeInterpolator.cc:161-188) on doubles: for every new time the
+ * pair (t1[i], t2[i]) of old positions it is blended from.  oldTimes: the old times in the new unit, strictly ascending (refused
+ * otherwise, as is nOld == 0).  Per new time pos = lower_bound(oldTimes + lastPos, oldTimes + nOld, x), with lastPos the pos of
+ * the step before (so a new axis that runs backwards gives what the reference gives); pos == nOld becomes nOld - 1; t2 = pos and
+ * t1 = pos - 1, except at pos == 0, where t1 = 0 and t2 = 1 if there is a second old time.  One old time gives (0, 0).
+ * Host arrays throughout; runs on the CPU and initialises nothing on a device.  nNew == 0 does nothing.
+ */
+int fimex_amd_time_mapping(const double* oldTimes, size_t nOld, const double* newTimes, size_t nNew, size_t* t1, size_t* t2);
+
+/** output steps per launch of fimex_amd_time_interpolate_device, and per chunk: a chunk re-reads the first pair it needs */
+#define FIMEX_AMD_TIME_LAUNCH_STEPS 128
+#define FIMEX_AMD_TIME_CHUNK_STEPS 32
+
+/**
+ * CDMTimeInterpolator::getDataSlice (src/CDMTimeInterpolator.cc:88-136) for every position of the new time axis in one pass:
+ * d_in [nOld][n] elements of cdmType (any of the ten numeric types), d_out float[nNew][n].  Output step i is
+ * mifi_get_values_linear_weak_extrapol_f (src/interpolation.c:1085-1109) on Data::asFloat() (a cast per element, no scale, no fill
+ * value handling) of the slices t1[i] and t2[i] of fimex_amd_time_mapping, with a = oldTimes[t1], b = oldTimes[t2], x = newTimes[i]:
+ *   f = (float)((x - a) / (b - a)), 0 where a == b
+ *   f == 0: a copy of A (a NaN in B does not leak in);  f == 1: a copy of B;  -1 <= f <= 2: A + f * (B - A) in float, uncontracted;
+ *   otherwise MIFI_UNDEFINED_F.  Bit for bit.
+ * The time arrays are host arrays and are free on return; the call only enqueues on `stream`.  A new axis that never runs backwards
+ * reads every input slice once per FIMEX_AMD_TIME_LAUNCH_STEPS output steps at most.  nOld must fit 32 bits.  d_out must not
+ * overlap d_in.  The times are checked first; after that n == 0 or nNew == 0 does nothing.
+ */
+int fimex_amd_time_interpolate_device(const void* d_in, int cdmType, size_t n, const double* oldTimes, size_t nOld, const double* newTimes,
+                                      size_t nNew, float* d_out, void* stream);
+
+/** The rules of CDMQualityExtractor (the "use" attribute of its configuration, or a list of status values). */
+typedef enum fimex_amd_quality_mode {
+    FIMEX_AMD_QUALITY_VALUES = 0, /* keep cells whose status is one of values[] */
+    FIMEX_AMD_QUALITY_ALL,        /* keep every defined status */
+    FIMEX_AMD_QUALITY_MAX,        /* "max:<limit>": a status above limit is undefined */
+    FIMEX_AMD_QUALITY_MIN,        /* "min:<limit>": a status below limit is undefined */
+    FIMEX_AMD_QUALITY_HIGHEST,    /* keep cells whose status is the largest defined status of the slice */
+    FIMEX_AMD_QUALITY_LOWEST      /* ... the smallest */
+} fimex_amd_quality_mode;
+
+/**
+ * CDMQualityExtractor::getDataSlice (src/CDMQualityExtractor.cc:239-391), in place: d_data[i] = fillValue wherever the status of
+ * cell i % nStatus fails the rule.  d_data: nData elements of dataType, d_status: nStatus elements of statusType, read as
+ * Data::asDouble(); both any of the ten numeric types.  nData must be a positive multiple of nStatus: the status repeats along
+ * the slow dimensions (:377-385).  Any other ratio is refused; the reference warns and passes the data on, which is the caller's
+ * part.  nData == 0 does nothing.
+ *   VALUES: masked where the status is none of values[nValues] (a host array; an empty list or a NaN in it is refused).
+ *           validMin, validMax and statusFill are ignored, as in the reference (:285-288).
+ *   the other modes: the status is undefined below validMin, above validMax and where it equals statusFill (NaN: no such bound),
+ *           then where the mode's rule says so (:304-361); masked where it is undefined.
+ *   A NaN status masks in every mode (:380).
+ * HIGHEST and LOWEST do what include/fimex/CDMQualityExtractor.h documents, not what findDefinedExtreme (:219-237) does
+ * (DESIGN.md divergence D8); with no defined status every cell is masked.
+ * fillValue goes through data_caster<C, double> (include/fimex/Utils.h:85-115): rounded half away from zero to int and cast for an
+ * integer type, a plain cast otherwise.  A fill the type cannot hold that way (the cast does not give the rounded value back; beyond
+ * the range of float) is refused.
+ * d_status may be d_data itself with one type and nStatus == nData (the reference's own-status case); any other overlap is refused.
+ * The call only enqueues on `stream`; values[] is free on return.
+ */
+int fimex_amd_quality_mask_device(void* d_data, int dataType, size_t nData, const void* d_status, int statusType, size_t nStatus, int mode,
+                                  const double* values, size_t nValues, double limit, double validMin, double validMax, double statusFill,
+                                  double fillValue, void* stream);
+
 /* ----------------------------------- plan building across projections (8f n2) */
 /* The reference calls PROJ.4 (pj_init_plus / pj_transform) here; this library carries its own projections:
  * latlong/longlat, stere, lcc, merc, tmerc, etmerc, utm, laea, aea, geos, omerc, sinu, cea, ortho, aeqd, nsper, ob_tran with o_proj=longlat (radians at this boundary for
