@@ -22,7 +22,7 @@ HOSTCLI = os.path.join(HERE, "host_cli")  # executable of the C++ host mirror (l
 STENCIL_LIB = os.path.join(HERE, "libstencil_math_host.so")  # csrc/stencil_math.hpp compiled for the CPU (tests/test_stencil_math_host.py)
 STENCIL_SHIM = os.path.join(ROOT, "tests", "stencil_math_host.hip")
 
-DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "regrid.hip", "staged.hip", "staged2.hip", "forward.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
+DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "regrid.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "forward.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
                   "time_accumulate.hip", "time_interpolate.hip", "quality.hip"]
 
 # -ffp-contract=off: the kernels reproduce the reference's IEEE arithmetic operation by operation

@@ -47,7 +47,7 @@ struct StagedPlan {
     DeviceArray<uint32_t> ldsA, ldsB;  // LDS offsets of stencil rows 0|1 (and 2|3 for bicubic), 16 bits each
 };
 
-// Second LDS-staged form (staged2.hip): tiles of one height and varying width (narrower where the source footprint of an
+// Second LDS-staged form (staged2_plan.hip builds it, staged2.hip and staged2_typed.hip run it): tiles of one height and varying width (narrower where the source footprint of an
 // output cell is larger, so that every tile fits the same LDS budget), workgroups of 256-1024 threads, and per tile the
 // list of 16-byte source chunks itself instead of row segments.
 struct StagedTile {
@@ -105,7 +105,7 @@ struct fimex_amd_regrid_plan {
     int useAlt = 0;
     size_t planBytesShape[2] = {0, 0};  // info.planBytes with either shape
 
-    // The second staged form for slices of 1- and 2-byte stored types (staged2.hip): built from this plan's own arrays on the
+    // The second staged form for slices of 1- and 2-byte stored types (staged2_typed.hip): built from this plan's own arrays on the
     // first typed apply of that element size, under the mutex (plans are shared by threads; everything else is immutable).
     struct TypedForms {
         std::mutex mtx;
@@ -159,9 +159,11 @@ void launch_staged_apply(const fimex_amd_regrid_plan& plan, const float* d_in, s
 bool launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                hipStream_t stream);
 
-// staged2.hip
+// staged2_plan.hip
 bool build_staged2_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
+// staged2.hip
 void launch_staged2_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+// staged2_typed.hip
 bool launch_staged2_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                 hipStream_t stream);
 

@@ -1,0 +1,112 @@
+// Second LDS-staged regrid form, what its three translation units share: staged2_plan.hip (tile scan, shape choice, plan),
+// staged2.hip (float kernel and launch), staged2_typed.hip (stored-type kernel, form cache and launch).
+#pragma once
+
+#include "plan.hpp"
+
+#include <algorithm>
+
+namespace fimex_amd {
+
+constexpr uint32_t kSpareBytes = 1024;  // one wave instruction of LDS-DMA behind the ring (see SliceRing, staged2_ring.hpp)
+
+// chunks of one slot: the workgroup's LDS less the spare KiB, in `depth` equal slots of whole wave instructions
+inline uint32_t slot_chunks(uint32_t ldsBytes, uint32_t depth)
+{
+    return ((ldsBytes - kSpareBytes) / depth / 16u) & ~63u;
+}
+
+struct Shape2 {
+    int nt, per, kmax;
+    uint32_t depth;         // slices of the ring: one or two in flight while one is interpolated
+    uint32_t tileW, tileH;  // widest tile
+    uint32_t ldsBytes;
+};
+
+// Checks a shape whose nt, per, tileW, ldsBytes and depth are set (from defaults or tuning switches), derives tileH and clamps
+// the LDS to what a workgroup may have.  Tile widths are multiples of `widthStep`.  false: no staged form with this shape.
+inline bool finish_shape(Shape2& sh, uint32_t widthStep)
+{
+    if (!(sh.nt == 256 || sh.nt == 512 || sh.nt == 1024)) return false;
+    const uint32_t outputs = (uint32_t)(sh.nt * sh.per);
+    if (sh.tileW < widthStep || sh.tileW % widthStep != 0 || outputs % sh.tileW != 0) return false;
+    sh.tileH = outputs / sh.tileW;
+    if (sh.ldsBytes > 160u * 1024u - 64u) sh.ldsBytes = 160u * 1024u - 64u;
+    if (sh.ldsBytes < 16u * 1024u) return false;
+    sh.depth = sh.depth == 3 ? 3u : 2u;
+    return true;
+}
+
+// staged2_plan.hip: tiles, chunk lists and LDS offsets of `form` for slices with `cpc` source cells per 16-byte chunk (4 for
+// float slices, 8 / 16 for 2- / 1-byte elements).  Where the stencil of an output cell lies: from the caller's positions (plan
+// creation), or, with d_px == nullptr -- the forms of stored types are built on first use, long after the positions are gone --
+// from the gather plan the positions were turned into.  false: no staged form (positions without spatial coherence).
+bool build_staged2_form(const fimex_amd_regrid_plan& plan, Staged2Plan& form, const double* d_px, const double* d_py, const Shape2& sh,
+                        uint32_t stripe, uint32_t cpc, hipStream_t stream);
+
+namespace {
+
+constexpr int kMaxZChunks = 31;
+
+struct Staged2Args {
+    const float* in;
+    float* out;
+    const StagedTile* tiles;
+    const uint32_t* order;
+    const uint32_t* chunkOff;
+    const uint32_t *ldsA, *ldsB;
+    const uint32_t* pos;  // gather plan (regrid.hip): source cell of the stencil's corner, for the tiles that are not staged
+    const float *xf, *yf;
+    const double *xfd, *yfd;
+    uint32_t outX, outY, tileH;
+    uint32_t inX;
+    uint32_t inBytes;    // one source slice
+    uint32_t nOut;
+    uint32_t nz;
+    uint32_t zStart[kMaxZChunks + 1];  // slices [zStart[c], zStart[c + 1]) belong to z chunk c
+    uint32_t nZChunks;    // > 0: flat grid, the z chunks of a tile are consecutive workgroups of one XCD; 0: z chunk = blockIdx.y
+    uint32_t slotChunks;  // 16-byte chunks of one slot of the slice ring (a multiple of 64: whole wave instructions)
+    uint32_t flags;      // tuning build only: 1 no source loads, 2 no result stores (STAGE2_ABLATE); the float kernel's store policy from 8 on
+};
+
+// everything of the kernels' argument but the z chunks: slices of elemBytes-byte elements through form `s` of the plan
+inline Staged2Args staged2_args(const fimex_amd_regrid_plan& plan, const Staged2Plan& s, const void* d_in, void* d_out, uint32_t elemBytes, size_t nz)
+{
+    Staged2Args a{};
+    a.in = static_cast<const float*>(d_in);
+    a.out = static_cast<float*>(d_out);
+    a.tiles = s.tiles.get();
+    a.order = s.order.get();
+    a.chunkOff = s.chunkOff.get();
+    a.ldsA = s.ldsA.get();
+    a.ldsB = s.ldsB.get();
+    a.pos = plan.pos.get();
+    a.xf = plan.xf.get();
+    a.yf = plan.yf.get();
+    a.xfd = plan.xfd.get();
+    a.yfd = plan.yfd.get();
+    a.outX = (uint32_t)plan.outX;
+    a.outY = (uint32_t)plan.outY;
+    a.tileH = s.tileH;
+    a.inX = (uint32_t)plan.inX;
+    a.inBytes = (uint32_t)(plan.inX * plan.inY * elemBytes);
+    a.nOut = (uint32_t)(plan.outX * plan.outY);
+    a.nz = (uint32_t)nz;
+    a.slotChunks = slot_chunks(s.ldsBytes, s.depth);
+    a.flags = (uint32_t)tuning("STAGE2_ABLATE", 0);
+    return a;
+}
+
+// n z chunks of one size (the first nz % n of them one slice longer), as consecutive workgroups of a tile
+inline void even_z_split(Staged2Args& a, size_t nz, uint32_t n)
+{
+    for (uint32_t c = 0, z = 0; c < n; ++c) {
+        a.zStart[c] = z;
+        z += (uint32_t)nz / n + (c < (uint32_t)nz % n ? 1u : 0u);
+    }
+    a.zStart[n] = (uint32_t)nz;
+    a.nZChunks = n;
+}
+
+}  // namespace
+}  // namespace fimex_amd

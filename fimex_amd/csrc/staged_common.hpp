@@ -1,5 +1,5 @@
 // Device helpers shared by the LDS-staged regrid kernels (staged.hip: one 256-thread workgroup per uniform tile;
-// staged2.hip: larger workgroups, tiles of varying width, slice ring of varying depth).
+// staged2*.hip: larger workgroups, tiles of varying width, slice ring of varying depth, see staged2_ring.hpp).
 #pragma once
 
 #include "plan.hpp"
