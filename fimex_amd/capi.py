@@ -68,6 +68,19 @@ class VerticalLevelsStruct(ctypes.Structure):
                 ("ps", ctypes.c_void_p), ("field", ctypes.c_void_p)]
 
 
+EXTRACT_MAX_DIMS = 8
+
+
+class ExtractDim(ctypes.Structure):
+    _fields_ = [("length", ctypes.c_size_t), ("reduced", ctypes.c_int), ("positions", ctypes.POINTER(ctypes.c_size_t)),
+                ("nPositions", ctypes.c_size_t), ("start", ctypes.c_size_t), ("size", ctypes.c_size_t)]
+
+
+class ExtractInfo(ctypes.Structure):
+    _fields_ = [("inElements", ctypes.c_size_t), ("outElements", ctypes.c_size_t), ("kernelDims", ctypes.c_size_t),
+                ("fastestRuns", ctypes.c_size_t), ("referenceOrderDiffers", ctypes.c_int)]
+
+
 _F = ctypes.POINTER(ctypes.c_float)
 _D = ctypes.POINTER(ctypes.c_double)
 _Z = ctypes.c_size_t
@@ -158,6 +171,12 @@ SYMBOLS = {
     "fimex_amd_time_interpolate_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _D, _Z, _D, _Z, _V, _V]),
     "fimex_amd_quality_mask_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, _V, ctypes.c_int, _Z, ctypes.c_int, _D, _Z, ctypes.c_double,
                                                      ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _V]),
+    "fimex_amd_extract_describe": (ctypes.c_int, [ctypes.POINTER(ExtractDim), _Z, ctypes.POINTER(ExtractInfo)]),
+    "fimex_amd_extract_plan_create": (ctypes.c_int, [ctypes.POINTER(ExtractDim), _Z, ctypes.POINTER(_V)]),
+    "fimex_amd_extract_plan_destroy": (ctypes.c_int, [_V]),
+    "fimex_amd_extract_plan_info": (ctypes.c_int, [_V, ctypes.POINTER(ExtractInfo)]),
+    "fimex_amd_extract_apply_device": (ctypes.c_int, [_V, _V, ctypes.c_int, _V, _V]),
+    "fimex_amd_extract_axis_range": (ctypes.c_int, [_D, _Z, ctypes.c_double, ctypes.c_double, _ZP, _ZP]),
     "fimex_amd_border_smooth_device": (ctypes.c_int, [_V, _V, _V, _Z, _Z, _Z, _Z, _Z, ctypes.c_int, _V]),
     "fimex_amd_border_smooth_host": (ctypes.c_int, [_F, _F, _F, _Z, _Z, _Z, _Z, _Z, ctypes.c_int]),
     "fimex_amd_overlay_device": (ctypes.c_int, [_V, _V, _V, _Z, _V]),
@@ -205,6 +224,13 @@ TIME_QUALITY_HOST_SYMBOLS = {
                                                    ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_extract_host.h declares: the entries of (8f n11) on host buffers
+EXTRACT_HOST_SYMBOLS = {
+    "fimex_amd_extract_apply_host": (ctypes.c_int, [_V, _V, ctypes.c_int, _V]),
+    "fimex_amd_extract_bounding_box_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _Z, _D, _Z, ctypes.c_int, ctypes.c_double,
+                                                           ctypes.c_double, ctypes.c_double, ctypes.c_double, _ZP, _ZP, _ZP, _ZP]),
+}
+
 _lib = None
 _libs = {}
 
@@ -219,7 +245,8 @@ def _open(path):
     except Exception:
         pass
     lib = ctypes.CDLL(path)
-    for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()):
+    for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
+            EXTRACT_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -929,6 +956,88 @@ def quality_mask_device(d_data, dataType, nData, d_status, statusType, nStatus, 
     v = _f64(values).reshape(-1)
     _check(load().fimex_amd_quality_mask_device(d_data, dataType, nData, d_status, statusType, nStatus, mode, _dp(v) if v.size else None, v.size,
                                                 limit, validMin, validMax, statusFill, fillValue, stream))
+
+
+def _extract_dims(dims):
+    """dims, fastest first: (length, positions) or (length, positions, start, size); positions None for a dimension that is not
+    reduced; without a window the whole reduced dimension is taken.  Returns the ctypes array and what it points into."""
+    arr = (ExtractDim * max(len(dims), 1))()
+    keep = []
+    for d, spec in zip(arr, dims):
+        length, positions = spec[0], spec[1]
+        d.length = length
+        d.reduced = int(positions is not None)
+        if positions is not None:
+            p = np.ascontiguousarray(positions, dtype=np.uintp).reshape(-1)
+            keep.append(p)
+            d.positions = p.ctypes.data_as(_ZP) if p.size else None
+            d.nPositions = p.size
+        d.start, d.size = (spec[2], spec[3]) if len(spec) > 2 else (0, length if positions is None else d.nPositions)
+    return arr, keep
+
+
+def extract_describe(dims):
+    """Checks a reduction (see _extract_dims) and returns the ExtractInfo of the plan it gives.  Runs on the CPU."""
+    arr, keep = _extract_dims(dims)
+    info = ExtractInfo()
+    _check(load().fimex_amd_extract_describe(arr, len(dims), ctypes.byref(info)))
+    return info
+
+
+class ExtractPlan:
+    """fimex_amd_extract_plan: CDMExtractor's data path for one variable, dims as for _extract_dims."""
+
+    def __init__(self, dims):
+        arr, keep = _extract_dims(dims)
+        self._lib = load()
+        self._h = _V()
+        _check(self._lib.fimex_amd_extract_plan_create(arr, len(dims), ctypes.byref(self._h)))
+        self.info = ExtractInfo()
+        _check(self._lib.fimex_amd_extract_plan_info(self._h, ctypes.byref(self.info)))
+        self.shape = tuple(int(d.size) for d in arr[:len(dims)])[::-1]  # slowest first, as numpy
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.fimex_amd_extract_plan_destroy(self._h)
+            self._h = _V()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown: module globals may be gone already
+            pass
+
+    def apply_device(self, d_in, cdmType, d_out, stream=0):
+        """d_in: info.inElements elements of cdmType, d_out: info.outElements.  Only enqueues on `stream`."""
+        _check(self._lib.fimex_amd_extract_apply_device(self._h, d_in, cdmType, d_out, stream))
+
+    def apply_host(self, data):
+        """A host array of a stored type with info.inElements elements: the reduced array, slowest dimension first."""
+        a = np.ascontiguousarray(data)
+        if a.size != self.info.inElements:
+            raise ValueError("data holds %d elements, the plan reads %d" % (a.size, self.info.inElements))
+        out = np.empty(self.shape, a.dtype)
+        _check(self._lib.fimex_amd_extract_apply_host(self._h, a.ctypes.data, cdm_type_of(a.dtype), out.ctypes.data))
+        return out
+
+
+def extract_axis_range(axis, startVal, endVal):
+    """The index arithmetic of CDMExtractor::reduceAxes on a 1-D axis in the unit of the bounds: (start, size).  Runs on the CPU."""
+    a = _f64(axis).reshape(-1)
+    start, size = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(load().fimex_amd_extract_axis_range(_dp(a) if a.size else None, a.size, startVal, endVal, ctypes.byref(start), ctypes.byref(size)))
+    return start.value, size.value
+
+
+def extract_bounding_box_host(proj_input, proj_lonlat, xAxis, yAxis, south, north, west, east, axesInDegree=False):
+    """CDMExtractor::reduceLatLonBoundingBox on two 1-D axes: the ascending x and y positions with a mesh point inside the box."""
+    x, y = _f64(xAxis).reshape(-1), _f64(yAxis).reshape(-1)
+    xp, yp = np.zeros(x.size, np.uintp), np.zeros(y.size, np.uintp)
+    nX, nY = ctypes.c_size_t(), ctypes.c_size_t()
+    _check(load().fimex_amd_extract_bounding_box_host(proj_input.encode(), proj_lonlat.encode(), _dp(x) if x.size else None, x.size,
+                                                      _dp(y) if y.size else None, y.size, int(bool(axesInDegree)), south, north, west, east,
+                                                      xp.ctypes.data_as(_ZP), ctypes.byref(nX), yp.ctypes.data_as(_ZP), ctypes.byref(nY)))
+    return xp[:nX.value].copy(), yp[:nY.value].copy()
 
 
 def border_smooth_host(inner, outerOnInner, transitionWidth=5, borderWidth=2, useOuterIfInnerUndefined=True):

@@ -13,7 +13,7 @@
 // seven-parameter shift is applied at height 0.  Everything else not implemented is refused (+units, +to_meter, +pm,
 // +geoc, +over, grid shifts).  +units / +to_meter scale the projected coordinates as pj_fwd / pj_inv do, +pm shifts
 // longitudes as pj_transform does.
-#include "plan.hpp"
+#include "extract.hpp"
 
 #include <cmath>
 #include <cstdio>
@@ -31,6 +31,7 @@ constexpr double kHalfPi = kPi / 2, kFortPi = kPi / 4;
 constexpr double kSpi = 3.14159265359;  // PROJ.4's adjlon threshold
 constexpr double kEps10 = 1e-10;
 constexpr double kDegToRad = .0174532925199432958;  // proj_api.h DEG_TO_RAD
+constexpr double kRadToDeg = 57.29577951308232;     // proj_api.h RAD_TO_DEG
 
 enum ProjKind { kLatLong = 0, kStere, kLcc, kMerc, kObTran, kTmerc, kEtmerc, kLaea, kAea, kGeos, kOmerc, kSinu, kCea, kOrtho, kAeqd, kNsper };
 enum StereMode { kNorth = 0, kSouth, kOblique, kEquatorial };
@@ -1347,6 +1348,35 @@ __global__ void __launch_bounds__(kBlock) project_axes_kernel(ProjParams src, Pr
     }
 }
 
+// reduceLatLonBoundingBox (src/CDMExtractor.cc:484-511): which columns and rows of the mesh of two axes hold a point inside the
+// box.  A wave takes 64 neighbouring ix of one iy; a lane transforms its point to degrees (Projection.cc:92-108) and tests it.
+// The flags are plain byte stores of the value 1, so lanes that race write the same thing.  A point whose transformation fails is
+// NaN here and lies outside every box (divergence D10).
+__global__ void __launch_bounds__(kBlock) bounding_box_kernel(ProjParams src, ProjParams dst, const double* __restrict__ xAxis,
+                                                              const double* __restrict__ yAxis, uint32_t nx, uint32_t ny, double south,
+                                                              double north, double west, double east, unsigned char* __restrict__ xKeep,
+                                                              unsigned char* __restrict__ yKeep)
+{
+    constexpr uint32_t kWaves = kBlock / kWave;
+    const uint32_t tiles = (nx + kWave - 1) / kWave, lane = threadIdx.x % kWave;
+    const size_t waves = (size_t)tiles * ny, stride = (size_t)gridDim.x * kWaves;
+    const bool wrap180 = west > east;  // :449
+    for (size_t w = (size_t)blockIdx.x * kWaves + threadIdx.x / kWave; w < waves; w += stride) {
+        const uint32_t iy = (uint32_t)(w / tiles), ix = (uint32_t)(w % tiles) * kWave + lane;
+        bool keep = false;
+        if (ix < nx) {
+            double lon = xAxis[ix], lat = yAxis[iy];
+            transform_point(src, dst, lon, lat);
+            lon *= kRadToDeg;
+            lat *= kRadToDeg;
+            keep = isfinite(lon) && isfinite(lat) && !(lat < south || lat > north) &&
+                   (wrap180 ? !(lon > east && lon < west) : !(lon < west || lon > east));  // :501-506
+            if (keep) xKeep[ix] = 1;
+        }
+        if (__any(keep) && lane == 0) yKeep[iy] = 1;
+    }
+}
+
 // interpolation.c:311-329
 __device__ __forceinline__ double bearing(double lat0, double lon0, double lat1, double lon1)
 {
@@ -1419,6 +1449,43 @@ void launch_project_axes(const char* projIn, const char* projOut, const double* 
     project_axes_kernel<<<point_blocks(ix * iy), kBlock, 0, stream>>>(src, dst, d_axes.get(), d_axes.get() + ix, (uint32_t)ix, (uint32_t)iy, d_outX, d_outY);
     FA_HIP(hipGetLastError());
     FA_HIP(hipStreamSynchronize(stream));  // d_axes is released on return
+}
+
+namespace {
+// stream-ordered scratch of one call, freed on the stream behind the work that uses it
+struct AsyncBytes {
+    void* p = nullptr;
+    hipStream_t stream;
+    AsyncBytes(size_t bytes, hipStream_t stream) : stream(stream) { FA_HIP(hipMallocAsync(&p, bytes, stream)); }
+    ~AsyncBytes() { if (p) (void)hipFreeAsync(p, stream); }
+    AsyncBytes(const AsyncBytes&) = delete;
+    AsyncBytes& operator=(const AsyncBytes&) = delete;
+};
+}  // namespace
+
+void run_bounding_box(const char* projIn, const char* projLonLat, const double* h_xAxis, size_t nx, const double* h_yAxis, size_t ny,
+                      bool axesInDegree, double south, double north, double west, double east, unsigned char* h_xKeep, unsigned char* h_yKeep,
+                      hipStream_t stream)
+{
+    const ProjPair pair = parse_pair(projIn, projLonLat);
+    if (nx * ny == 0) return;
+    FA_REQUIRE(nx <= 0x7FFFFFFFu && ny <= 0x7FFFFFFFu, "axis too long");
+    std::vector<double> axes(nx + ny);
+    for (size_t i = 0; i < nx; ++i) axes[i] = axesInDegree ? h_xAxis[i] * kDegToRad : h_xAxis[i];  // Projection.cc:81-90
+    for (size_t i = 0; i < ny; ++i) axes[nx + i] = axesInDegree ? h_yAxis[i] * kDegToRad : h_yAxis[i];
+    const size_t axisBytes = (nx + ny) * sizeof(double);
+    AsyncBytes scratch(axisBytes + nx + ny, stream);
+    double* d_axes = static_cast<double*>(scratch.p);
+    unsigned char* d_keep = static_cast<unsigned char*>(scratch.p) + axisBytes;
+    FA_HIP(hipMemcpyAsync(d_axes, axes.data(), axisBytes, hipMemcpyHostToDevice, stream));
+    FA_HIP(hipMemsetAsync(d_keep, 0, nx + ny, stream));
+    const size_t waves = ceil_div(nx, (size_t)kWave) * ny;
+    bounding_box_kernel<<<point_blocks(waves * kWave), kBlock, 0, stream>>>(pair.src, pair.dst, d_axes, d_axes + nx, (uint32_t)nx, (uint32_t)ny,
+                                                                            south, north, west, east, d_keep, d_keep + nx);
+    FA_HIP(hipGetLastError());
+    FA_HIP(hipMemcpyAsync(h_xKeep, d_keep, nx, hipMemcpyDeviceToHost, stream));
+    FA_HIP(hipMemcpyAsync(h_yKeep, d_keep + nx, ny, hipMemcpyDeviceToHost, stream));
+    FA_HIP(hipStreamSynchronize(stream));  // axes and the caller's flags are in use until here
 }
 
 namespace {

@@ -764,6 +764,62 @@ int fimex_amd_quality_mask_device(void* d_data, int dataType, size_t nData, cons
                                   const double* values, size_t nValues, double limit, double validMin, double validMax, double statusFill,
                                   double fillValue, void* stream);
 
+/* ------------------------------------------------------- extraction (8f n11) */
+/* CDMExtractor's data path (src/CDMExtractor.cc): a variable with some dimensions reduced to picked positions, read through a
+ * SliceBuilder window, and the index computations behind reduceTime / reduceVerticalAxis and reduceLatLonBoundingBox. */
+#define FIMEX_AMD_EXTRACT_MAX_DIMS 8
+
+typedef struct fimex_amd_extract_dim {
+    size_t length;            /* length of the dimension in the source */
+    int reduced;              /* 0: not in dimSlices_, every position is taken; positions and nPositions are ignored */
+    const size_t* positions;  /* host array, strictly ascending, every entry < length; may be NULL when nPositions == 0 */
+    size_t nPositions;
+    size_t start, size;       /* the SliceBuilder window in the reduced dimension: start + size <= (reduced ? nPositions : length) */
+} fimex_amd_extract_dim;      /* dims[0] is the fastest dimension */
+
+typedef struct fimex_amd_extract_info {
+    size_t inElements, outElements;
+    size_t kernelDims;          /* dimensions left after folding lengths of 1 and merging whole neighbours (0: nothing to move) */
+    size_t fastestRuns;         /* contiguous source runs of one output row of the merged fastest dimension */
+    int referenceOrderDiffers;  /* divergence D9: the reference's joinSlices emits these elements in another order */
+} fimex_amd_extract_info;
+
+/** Opaque, immutable extraction plan: the offset tables of one variable's reduction, resident in HBM. */
+typedef struct fimex_amd_extract_plan fimex_amd_extract_plan;
+
+/**
+ * Checks a reduction and describes the plan it gives; runs on the CPU and initialises nothing on a device.  Refused: nDims == 0
+ * or above FIMEX_AMD_EXTRACT_MAX_DIMS, a dimension of length 0 with a non-empty window, positions that are not strictly ascending
+ * or reach the length, a window beyond the reduced length, NULL where an array is needed, a source of more elements than size_t
+ * counts.  referenceOrderDiffers: the output holds an element, some reduced dimension's window is cut into more than one run of
+ * neighbouring positions, and a slower dimension that is not reduced has a window longer than 1 (src/CDMExtractor.cc:96-179 then
+ * emits run-major data under a row-major shape; the apply entries below always give the row-major array).
+ */
+int fimex_amd_extract_describe(const fimex_amd_extract_dim* dims, size_t nDims, fimex_amd_extract_info* info);
+/** The same checks, then the tables are built and uploaded to the calling thread's device.  dims and the position arrays are free
+ *  on return. */
+int fimex_amd_extract_plan_create(const fimex_amd_extract_dim* dims, size_t nDims, fimex_amd_extract_plan** plan);
+int fimex_amd_extract_plan_destroy(fimex_amd_extract_plan* plan);
+int fimex_amd_extract_plan_info(const fimex_amd_extract_plan* plan, fimex_amd_extract_info* info);
+/**
+ * CDMExtractor::getDataSlice_ (src/CDMExtractor.cc:96-179) for one variable.  With p_d(i) = positions_d[start_d + i] for a reduced
+ * dimension and start_d + i otherwise, out is the row-major array out[i_{n-1}]...[i_0] = in[p_{n-1}(i_{n-1})]...[p_0(i_0)] of
+ * info.outElements elements; in holds info.inElements elements.  cdmType: any of the ten numeric fimex_amd_datatype values; only
+ * its element size matters, bytes are moved and never interpreted.  Both pointers must be aligned to the element size; out must
+ * not overlap in.  outElements == 0 does nothing and accepts NULL pointers.  A plan is immutable: apply may run from several
+ * threads and streams at once.  The call only enqueues on `stream` and must run on the plan's device.
+ */
+int fimex_amd_extract_apply_device(const fimex_amd_extract_plan* plan, const void* d_in, int cdmType, void* d_out, void* stream);
+/**
+ * The index arithmetic of CDMExtractor::reduceAxes (src/CDMExtractor.cc:369-406) on a 1-D axis already in the unit of startVal and
+ * endVal (units.convert stays with the caller): delta = 1e-5, or 0.01 * |axis[0] - axis[1]| when these differ; a descending axis
+ * (axis[0] > axis[1]) is searched reversed; start = lower_bound(startVal - delta), end = upper_bound(endVal + delta),
+ * size = max(end - start, 0), and start = n - size - start on a descending axis.  n == 0 gives (0, 0).  A NaN in the axis or
+ * in the bounds is refused.  Runs on the CPU and initialises nothing on a device.
+ */
+int fimex_amd_extract_axis_range(const double* axis, size_t n, double startVal, double endVal, size_t* start, size_t* size);
+/* The *_host form of the apply and the bounding box on host axes are declared in fimex_amd_extract_host.h. */
+
 /* ----------------------------------- plan building across projections (8f n2) */
 /* The reference calls PROJ.4 (pj_init_plus / pj_transform) here; this library carries its own projections:
  * latlong/longlat, stere, lcc, merc, tmerc, etmerc, utm, laea, aea, geos, omerc, sinu, cea, ortho, aeqd, nsper, ob_tran with o_proj=longlat (radians at this boundary for
