@@ -81,6 +81,11 @@ class ExtractInfo(ctypes.Structure):
                 ("fastestRuns", ctypes.c_size_t), ("referenceOrderDiffers", ctypes.c_int)]
 
 
+class VerticalInfo(ctypes.Structure):
+    _fields_ = [("nx", ctypes.c_size_t), ("ny", ctypes.c_size_t), ("nt", ctypes.c_size_t), ("nzi", ctypes.c_size_t), ("nzo", ctypes.c_size_t),
+                ("method", ctypes.c_int), ("entryBytes", ctypes.c_size_t)]
+
+
 _F = ctypes.POINTER(ctypes.c_float)
 _D = ctypes.POINTER(ctypes.c_double)
 _Z = ctypes.c_size_t
@@ -142,6 +147,11 @@ SYMBOLS = {
                                                              _V, _V]),
     "fimex_amd_vertical_interpolate_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, _F, ctypes.POINTER(VerticalLevelsStruct),
                                                            ctypes.POINTER(VerticalLevelsStruct), _D, _Z, _D, _D, ctypes.c_float, ctypes.c_float, _F]),
+    "fimex_amd_vertical_plan_create_device": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, ctypes.POINTER(VerticalLevelsStruct),
+                                                             ctypes.POINTER(VerticalLevelsStruct), _D, _Z, _V, _V, _V, ctypes.POINTER(_V)]),
+    "fimex_amd_vertical_plan_destroy": (ctypes.c_int, [_V]),
+    "fimex_amd_vertical_plan_info": (ctypes.c_int, [_V, ctypes.POINTER(VerticalInfo)]),
+    "fimex_amd_vertical_plan_apply_device": (ctypes.c_int, [_V, _Z, ctypes.POINTER(_V), ctypes.c_int, _D, _F, _F, ctypes.POINTER(_V), _V]),
     "fimex_amd_vertical_levels_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V]),
     "fimex_amd_vertical_levels_host": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _F]),
     "fimex_amd_vertical_altitude_integrate_device": (ctypes.c_int, [ctypes.POINTER(VerticalLevelsStruct), _Z, _Z, _Z, _V, _V, _V, _V, ctypes.c_int,
@@ -231,6 +241,14 @@ EXTRACT_HOST_SYMBOLS = {
                                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, _ZP, _ZP, _ZP, _ZP]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_vertical_plan_host.h declares: the entries of (8f n5b) on host buffers
+VERTICAL_PLAN_HOST_SYMBOLS = {
+    "fimex_amd_vertical_plan_create_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, ctypes.POINTER(VerticalLevelsStruct),
+                                                           ctypes.POINTER(VerticalLevelsStruct), _D, _Z, _D, _D, ctypes.POINTER(_V)]),
+    "fimex_amd_vertical_plan_apply_host": (ctypes.c_int, [_V, _Z, ctypes.POINTER(_V), ctypes.c_int, _D, _F, _F, ctypes.POINTER(_V)]),
+    "fimex_amd_vertical_plan_read_host": (ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), _F]),
+}
+
 _lib = None
 _libs = {}
 
@@ -246,7 +264,7 @@ def _open(path):
         pass
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
-            EXTRACT_HOST_SYMBOLS.items()):
+            EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -692,6 +710,80 @@ def vertical_interpolate_device(method, nx, ny, nt, d_in, inLevels, d_out, outLe
     _check(load().fimex_amd_vertical_interpolate_device(method, nx, ny, nt, d_in, _levels_ref(inLevels), _levels_ref(outLevels),
                                                         _dp(l1) if l1 is not None else None, nzo, d_validMin, d_validMax,
                                                         clampMin, clampMax, d_out, stream))
+
+
+class VerticalPlan:
+    """fimex_amd_vertical_plan: the search of vertical_interpolate_* for one set of levels, kept on the device and applied to every
+    variable that shares it.  Arguments as for vertical_interpolate_device (device=True: ps / field of the level descriptions,
+    validMin and validMax are device pointers and the build is only enqueued on `stream`) or vertical_interpolate_host."""
+
+    def __init__(self, method, nx, ny, nt, inLevels, outLevels=None, level1=None, validMin=None, validMax=None, device=False, stream=0):
+        l1 = _f64(level1).ravel() if level1 is not None else None
+        nzo = outLevels.nz if outLevels is not None else (l1.size if l1 is not None else 0)
+        self._lib = load()
+        self._h = _V()
+        head = (method, nx, ny, nt, _levels_ref(inLevels), _levels_ref(outLevels), _dp(l1) if l1 is not None else None, nzo)
+        if device:
+            _check(self._lib.fimex_amd_vertical_plan_create_device(*head, validMin, validMax, stream, ctypes.byref(self._h)))
+        else:
+            vmin = _f64(validMin).reshape(-1) if validMin is not None else None
+            vmax = _f64(validMax).reshape(-1) if validMax is not None else None
+            _check(self._lib.fimex_amd_vertical_plan_create_host(*head, _dp(vmin) if vmin is not None else None,
+                                                                 _dp(vmax) if vmax is not None else None, ctypes.byref(self._h)))
+        self.info = VerticalInfo()
+        _check(self._lib.fimex_amd_vertical_plan_info(self._h, ctypes.byref(self.info)))
+        self.in_shape = (self.info.nt, self.info.nzi, self.info.ny, self.info.nx)
+        self.out_shape = (self.info.nt, self.info.nzo, self.info.ny, self.info.nx)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.fimex_amd_vertical_plan_destroy(self._h)
+            self._h = _V()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # interpreter shutdown: module globals may be gone already
+            pass
+
+    @staticmethod
+    def _per_variable(nvar, badValue, clampMin, clampMax):
+        spread = lambda v, dt: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dt), (nvar,)))
+        return spread(badValue, np.float64), spread(clampMin, np.float32), spread(clampMax, np.float32)
+
+    def apply_device(self, d_in, cdmType, d_out, badValue=float("nan"), clampMin=float("nan"), clampMax=float("nan"), stream=0):
+        """d_in / d_out: one device pointer or a sequence of them, variables of cdmType [nt][nzi][ny][nx] -> [nt][nzo][ny][nx];
+        badValue, clampMin, clampMax: one value for all or one per variable.  Only enqueues on `stream`."""
+        ins = [d_in] if isinstance(d_in, int) else list(d_in)
+        outs = [d_out] if isinstance(d_out, int) else list(d_out)
+        if len(ins) != len(outs):
+            raise ValueError("as many outputs as inputs")
+        n = len(ins)
+        bad, cmin, cmax = self._per_variable(n, badValue, clampMin, clampMax)
+        _check(self._lib.fimex_amd_vertical_plan_apply_device(self._h, n, (_V * max(n, 1))(*ins), cdmType, _dp(bad), _fp(cmin), _fp(cmax),
+                                                              (_V * max(n, 1))(*outs), stream))
+
+    def apply_host(self, data, badValue=float("nan"), clampMin=float("nan"), clampMax=float("nan")):
+        """One host array [nt][nzi][ny][nx] of a stored type, or a sequence of them of one type: the interpolated array(s)."""
+        single = isinstance(data, np.ndarray)
+        arrs = [np.ascontiguousarray(a) for a in ([data] if single else data)]
+        n = len(arrs)
+        for a in arrs:
+            if a.dtype != arrs[0].dtype or a.size != int(np.prod(self.in_shape)):
+                raise ValueError("every variable holds %r elements of one type" % (self.in_shape,))
+        outs = [np.empty(self.out_shape, arrs[0].dtype) for _ in arrs]
+        bad, cmin, cmax = self._per_variable(n, badValue, clampMin, clampMax)
+        _check(self._lib.fimex_amd_vertical_plan_apply_host(self._h, n, (_V * n)(*[a.ctypes.data for a in arrs]), cdm_type_of(arrs[0].dtype),
+                                                            _dp(bad), _fp(cmin), _fp(cmax), (_V * n)(*[o.ctypes.data for o in outs])))
+        return outs[0] if single else outs
+
+    def entries(self):
+        """(first, second, factor), each [nt][nzo][ny][nx]; an undefined entry has first == second."""
+        first, second = np.empty(self.out_shape, np.uint32), np.empty(self.out_shape, np.uint32)
+        factor = np.empty(self.out_shape, np.float32)
+        u = ctypes.POINTER(ctypes.c_uint)
+        _check(self._lib.fimex_amd_vertical_plan_read_host(self._h, first.ctypes.data_as(u), second.ctypes.data_as(u), _fp(factor)))
+        return first, second, factor
 
 
 def vertical_levels_host(levels, nx, ny, nt):

@@ -17,17 +17,6 @@ using namespace fimex_amd;
 
 namespace {
 
-// the device form demands the plan's device, the host form switches to it for the call
-struct PlanDevice {
-    bool switchTo;
-    std::optional<ScopedDevice> scoped;
-    void enter(int device)
-    {
-        if (switchTo) scoped.emplace(device);
-        else require_current_device(device);
-    }
-};
-
 template <class Call>
 void extract_apply(Call&& c, PlanDevice& dev, const fimex_amd_extract_plan* plan, const void* in, int cdmType, void* out)
 {

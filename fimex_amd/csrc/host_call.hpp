@@ -100,6 +100,17 @@ struct DeviceCall {
     void finish() const {}
 };
 
+// the device of a plan object in an apply: the device form demands it, the host form switches to it for the call
+struct PlanDevice {
+    bool switchTo;
+    std::optional<ScopedDevice> scoped;
+    void enter(int device)
+    {
+        if (switchTo) scoped.emplace(device);
+        else require_current_device(device);
+    }
+};
+
 // a level description for the launch: the caller's own for a device call, with device copies of its 2-D / 3-D members for a
 // host call
 inline fimex_amd_vertical_levels levels_on(const DeviceCall&, const fimex_amd_vertical_levels& l, size_t, size_t) { return l; }

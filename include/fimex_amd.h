@@ -431,6 +431,60 @@ int fimex_amd_vertical_interpolate_host(int method, size_t nx, size_t ny, size_t
 int fimex_amd_vertical_levels_device(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* d_out, void* stream);
 int fimex_amd_vertical_levels_host(const fimex_amd_vertical_levels* levels, size_t nx, size_t ny, size_t nt, float* out);
 
+/* ------------------------------- vertical interpolation plans (8f n5b) */
+/* The search of fimex_amd_vertical_interpolate_* depends on the input levels, the target levels, the validity range and the method,
+ * never on the variable.  A plan holds its result per (unlimited-dimension position, output level, column): the pair of input
+ * levels and the blend factor with the method folded in, 8 bytes per output cell.  The apply gathers two values per cell, blends,
+ * clamps and stores, on the variable's stored type and for several variables in one call.  The reference has no such object: the
+ * arithmetic is getLevelDataSlice's, the split is this library's. */
+
+/** Opaque, immutable vertical interpolation plan, resident in HBM. */
+typedef struct fimex_amd_vertical_plan fimex_amd_vertical_plan;
+
+typedef struct fimex_amd_vertical_info {
+    size_t nx, ny, nt;
+    size_t nzi, nzo;
+    int method;         /* FIMEX_AMD_VINT_METHOD_* */
+    size_t entryBytes;  /* bytes of the entries on the device */
+} fimex_amd_vertical_info;
+
+/**
+ * Runs the search of fimex_amd_vertical_interpolate_device for every output cell and keeps its result; every argument means what
+ * it means there.  Allocates the entries on the calling thread's device, enqueues the build on `stream` and returns.  ps, field,
+ * d_validMin and d_validMax are read by the build only; level1 and the coefficient arrays are free on return.  The plan may be
+ * applied on the same stream at once, and on another stream once the caller has ordered that stream behind the build.
+ * Refused, before any device is initialised: an unknown method or level kind, NULL where a kind needs an array, fixed levels
+ * without level1, nzi == 0, nzo == 0, nzi > 65535 (an entry holds a level index in 16 bits), nt > 65535.
+ * Lifetime, as for the other plan objects: the plan belongs to the device it was created on and to the library that made it;
+ * it is immutable, so any number of threads and streams may apply it at once; destroy it only after every apply that was
+ * enqueued with it has finished, and on no stream's behalf does the library wait for that.
+ */
+int fimex_amd_vertical_plan_create_device(int method, size_t nx, size_t ny, size_t nt, const fimex_amd_vertical_levels* inLevels,
+                                          const fimex_amd_vertical_levels* outLevels, const double* level1, size_t nzo,
+                                          const double* d_validMin, const double* d_validMax, void* stream,
+                                          fimex_amd_vertical_plan** plan);
+int fimex_amd_vertical_plan_destroy(fimex_amd_vertical_plan* plan);
+int fimex_amd_vertical_plan_info(const fimex_amd_vertical_plan* plan, fimex_amd_vertical_info* info);
+/**
+ * getLevelDataSlice for nvar >= 1 variables that share the plan, on their stored type cdmType (one of the ten numeric
+ * fimex_amd_datatype values): d_in[i] [nt][nzi][ny][nx] -> d_out[i] [nt][nzo][ny][nx] of the same type.  d_in, badValue, clampMin,
+ * clampMax and d_out are HOST arrays of length nvar; d_in[] and d_out[] hold device pointers.  Per output cell: an undefined entry
+ * gives NaN; otherwise A and B are the two data values as data2InterpolationArray reads them (static_cast to float, badValue[i]
+ * as NaN; a NaN badValue changes nothing) and v = f == 0 ? A : f == 1 ? B : A + f * (B - A); v is clamped to
+ * [clampMin[i], clampMax[i]] (NaN: no bound) and stored as interpolationArray2Data stores it (NaN as badValue[i], integers
+ * rounded).  This is fimex_amd_data2interpolation_device, fimex_amd_vertical_interpolate_device and
+ * fimex_amd_interpolation2data_device in one pass, byte for byte, with no float copy of the variable.  One case apart: cdmType
+ * FLOAT with a NaN badValue is an interpolation array as fimex_amd_vertical_interpolate_device takes it; it is read and stored
+ * unchanged and the result is that entry's bit for bit (the three calls would turn a -0.0 into +0.0).
+ * The library groups the variables into launches of its choice; a launch reads the entries once for its variables.  Outputs must
+ * not overlap each other, an input or the plan.  Pointers must be aligned to the element size, and nothing more.  Only enqueues
+ * on `stream`; must run on the plan's device.
+ */
+int fimex_amd_vertical_plan_apply_device(const fimex_amd_vertical_plan* plan, size_t nvar, const void* const* d_in, int cdmType,
+                                         const double* badValue, const float* clampMin, const float* clampMax, void* const* d_out,
+                                         void* stream);
+/* The *_host forms of create and apply, and the entries read back to the host, are declared in fimex_amd_vertical_plan_host.h. */
+
 /* ------------------------ vertical level converters: altitude, height, depth (8f n6) */
 /* What the reference's VerticalConverter chain (src/coordSys/verticalTransform/) puts into verticalData4D for the vertical
  * types MIFI_VINT_ALTITUDE, MIFI_VINT_HEIGHT and MIFI_VINT_DEPTH: an f32 field [nt][nz][ny][nx], which
