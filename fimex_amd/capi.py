@@ -119,6 +119,7 @@ SYMBOLS = {
     "fimex_amd_vector_plan_destroy": (ctypes.c_int, [_V]),
     "fimex_amd_vector_reproject_values_host": (ctypes.c_int, [_V, _F, _F, _Z]),
     "fimex_amd_vector_reproject_values_device": (ctypes.c_int, [_V, _V, _V, _Z, _V]),
+    "fimex_amd_regrid_apply_vector_device": (ctypes.c_int, [_V, _V, _V, _V, _Z, _V, _V, _V, ctypes.POINTER(ctypes.c_int)]),
     "fimex_amd_vector_reproject_direction_host": (ctypes.c_int, [_V, _F, _Z]),
     "fimex_amd_vector_reproject_direction_device": (ctypes.c_int, [_V, _V, _Z, _V]),
     "fimex_amd_fill2d_host": (ctypes.c_int, [_Z, _Z, _Z, _F, ctypes.c_float, ctypes.c_float, _Z, _ZP]),
@@ -241,6 +242,11 @@ EXTRACT_HOST_SYMBOLS = {
                                                            ctypes.c_double, ctypes.c_double, ctypes.c_double, _ZP, _ZP, _ZP, _ZP]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_vector_regrid_host.h declares: a vector pair regridded and rotated on host buffers
+VECTOR_REGRID_HOST_SYMBOLS = {
+    "fimex_amd_regrid_apply_vector_host": (ctypes.c_int, [_V, _V, _F, _F, _Z, _F, _F, _Z, _ZP]),
+}
+
 # name -> (restype, argtypes); every symbol include/fimex_amd_vertical_plan_host.h declares: the entries of (8f n5b) on host buffers
 VERTICAL_PLAN_HOST_SYMBOLS = {
     "fimex_amd_vertical_plan_create_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, ctypes.POINTER(VerticalLevelsStruct),
@@ -264,7 +270,7 @@ def _open(path):
         pass
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
-            EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()):
+            EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()) + list(VECTOR_REGRID_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -381,6 +387,24 @@ class RegridPlan:
 
     def apply_device(self, d_in, nz, d_out, stream=0):
         _check(load().fimex_amd_regrid_apply_device(self._h, d_in, nz, d_out, stream))
+
+    def apply_vector_device(self, vec, d_u, d_v, nz, d_uOut, d_vOut, stream=0):
+        """getDataSlice's vector branch on device buffers: both components regridded and rotated by `vec` (a VectorPlan on the
+        output grid).  Returns the path: 1 the fused kernel, 0 regrid, regrid, rotate."""
+        path = ctypes.c_int(-1)
+        _check(load().fimex_amd_regrid_apply_vector_device(self._h, vec._h, d_u, d_v, nz, d_uOut, d_vOut, stream, ctypes.byref(path)))
+        return path.value
+
+    def apply_vector_host(self, vec, u, v):
+        """The same on [nz][inY][inX] float32 host arrays; returns (uOut, vOut), each [nz][outY][outX]."""
+        a, b = _f32(u).ravel(), _f32(v).ravel()
+        if a.size != b.size:
+            raise ValueError("the components differ in size")
+        nz = a.size // (self.inX * self.inY) if self.inX * self.inY else 0
+        uOut, vOut = (np.empty(nz * self.outX * self.outY, dtype=np.float32) for _ in range(2))
+        n = _Z(0)
+        _check(load().fimex_amd_regrid_apply_vector_host(self._h, vec._h, _fp(a), _fp(b), a.size, _fp(uOut), _fp(vOut), uOut.size, ctypes.byref(n)))
+        return uOut.reshape(-1, self.outY, self.outX), vOut.reshape(-1, self.outY, self.outX)
 
     def apply_gather_device(self, d_in, nz, d_out, stream=0):
         """The same regrid through the per-lane gather kernels (cross-check of the staged kernels on whole batches)."""

@@ -1,8 +1,13 @@
 // extern "C" boundary, vectors and projections: the vector reprojection plan and its applies (vector.hip), the proj-level entries
-// (projection.hip), the coordinate searches (coordsearch.hip) and points2position (convert.hip).
+// (projection.hip), the coordinate searches (coordsearch.hip), points2position (convert.hip), and the regrid of a vector pair
+// with its rotation (staged2_vector.hip, or the three launches it replaces).
+#include "capi_checks.hpp"
 #include "host_call.hpp"
 
+#include "../../include/fimex_amd_vector_regrid_host.h"
+
 #include <memory>
+#include <string>
 
 using namespace fimex_amd;
 
@@ -52,6 +57,38 @@ void check_coord_search_host(const double* px, const double* py, size_t nPoints,
 {
     FA_REQUIRE(nPoints == 0 || (px != nullptr && py != nullptr), "NULL argument");
     FA_REQUIRE(n == 0 || (lon != nullptr && lat != nullptr), "NULL argument");
+}
+
+// what both forms of regrid_apply_vector refuse; the buffers are the caller's own pointers, host or device
+void check_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* u, const float* v, size_t nz,
+                       const float* uOut, const float* vOut)
+{
+    FA_REQUIRE(plan.kind != PlanKind::Forward, "a vector pair is regridded with a backward plan, this is a forward plan");
+    FA_REQUIRE(vec.ox == plan.outX && vec.oy == plan.outY, "the vector plan's grid (ox, oy) differs from the regrid plan's output grid (outX, outY)");
+    FA_REQUIRE(vec.device == plan.device, "the regrid plan and the vector plan live on different devices");
+    const size_t inBytes = nz * plan.inX * plan.inY * sizeof(float), outBytes = nz * plan.outX * plan.outY * sizeof(float);
+    const Span b[4] = {{u, inBytes, "u"}, {v, inBytes, "v"}, {uOut, outBytes, "uOut"}, {vOut, outBytes, "vOut"}};
+    for (int i = 0; i < 4; ++i)
+        for (int j = i + 1; j < 4; ++j) {
+            const char *p = static_cast<const char*>(b[i].p), *q = static_cast<const char*>(b[j].p);
+            FA_REQUIRE(!b[i].bytes || !b[j].bytes || p + b[i].bytes <= q || q + b[j].bytes <= p,
+                       std::string("buffers overlap: ") + b[i].name + " and " + b[j].name);
+        }
+}
+
+// CDMInterpolator.cc:259-277 on device buffers: the fused kernel where it serves the plan and the batch, else the chain it
+// replaces, launch for launch; returns the path taken
+int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
+                      float* d_uOut, float* d_vOut, hipStream_t stream)
+{
+    if (staged2_vector_serves(plan, nz)) {
+        launch_staged2_apply_vector(plan, vec, d_u, d_v, nz, d_uOut, d_vOut, stream);
+        return 1;
+    }
+    apply_plan_device(plan, d_u, nz, d_uOut, stream);
+    apply_plan_device(plan, d_v, nz, d_vOut, stream);
+    launch_vector_values(vec, d_uOut, d_vOut, nz, stream);
+    return 0;
 }
 
 }  // namespace
@@ -108,6 +145,44 @@ int fimex_amd_vector_reproject_values_device(const fimex_amd_vector_plan* plan, 
         FA_REQUIRE(d_u != nullptr && d_v != nullptr, "NULL device buffer");
         require_current_device(plan->device);
         launch_vector_values(*plan, d_u, d_v, oz, as_stream(stream));
+    });
+}
+
+int fimex_amd_regrid_apply_vector_device(const fimex_amd_regrid_plan* plan, const fimex_amd_vector_plan* vec, const float* d_u, const float* d_v,
+                                         size_t nz, float* d_uOut, float* d_vOut, void* stream, int* path)
+{
+    return c_guard([&] {
+        if (path) *path = 0;
+        FA_REQUIRE(plan != nullptr, "NULL regrid plan");
+        FA_REQUIRE(vec != nullptr, "NULL vector plan");
+        FA_REQUIRE(nz == 0 || (d_u != nullptr && d_v != nullptr && d_uOut != nullptr && d_vOut != nullptr), "NULL device buffer");
+        check_vector_pair(*plan, *vec, d_u, d_v, nz, d_uOut, d_vOut);
+        if (nz == 0) return;
+        require_current_device(plan->device);
+        const int taken = apply_vector_pair(*plan, *vec, d_u, d_v, nz, d_uOut, d_vOut, as_stream(stream));
+        if (path) *path = taken;
+    });
+}
+
+int fimex_amd_regrid_apply_vector_host(const fimex_amd_regrid_plan* plan, const fimex_amd_vector_plan* vec, const float* u, const float* v,
+                                       size_t size, float* uOut, float* vOut, size_t outCapacity, size_t* newSize)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL regrid plan");
+        FA_REQUIRE(vec != nullptr, "NULL vector plan");
+        FA_REQUIRE(newSize != nullptr, "NULL argument");
+        const size_t inLayer = plan->inX * plan->inY, outLayer = plan->outX * plan->outY;
+        const size_t nz = inLayer ? size / inLayer : 0;  // CachedInterpolation.cc:121
+        *newSize = outLayer * nz;                         // :122
+        FA_REQUIRE(nz == 0 || (u != nullptr && v != nullptr && uOut != nullptr && vOut != nullptr), "NULL buffer");
+        check_vector_pair(*plan, *vec, u, v, nz, uOut, vOut);
+        if (nz == 0) return;
+        FA_REQUIRE(outCapacity >= *newSize, "output buffers too small");
+        ScopedDevice dev(plan->device);
+        HostCall hc;
+        const float *d_u = hc.in(u, nz * inLayer), *d_v = hc.in(v, nz * inLayer);
+        apply_vector_pair(*plan, *vec, d_u, d_v, nz, hc.out(uOut, nz * outLayer), hc.out(vOut, nz * outLayer), hc.stream());
+        hc.finish();
     });
 }
 

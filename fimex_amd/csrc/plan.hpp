@@ -163,6 +163,11 @@ bool launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_
 bool build_staged2_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
 // staged2.hip
 void launch_staged2_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+// staged2_vector.hip: both components of a vector pair regridded and rotated in one launch; `serves` is the dispatch rule
+// (nearest / bilinear plans with the second staged form, batches of staged_min_nz() pairs and more, VECTOR_FUSED not 0)
+bool staged2_vector_serves(const fimex_amd_regrid_plan& plan, size_t nz);
+void launch_staged2_apply_vector(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
+                                 float* d_uOut, float* d_vOut, hipStream_t stream);
 // staged2_typed.hip
 bool launch_staged2_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                 hipStream_t stream);

@@ -239,37 +239,10 @@ void launch_shape(const Staged2Plan& s, const Staged2Args& a, dim3 grid, hipStre
 
 void launch_staged2_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream)
 {
-    const int forced = tuning("STAGE2_USE_ALT", -1);  // tuning build: 0 / 1 overrides the plan's choice
-    const bool alt = plan.staged2Alt.valid && (forced >= 0 ? forced == 1 : plan.useAlt != 0);
-    const Staged2Plan& s = alt ? plan.staged2Alt : plan.staged2;
+    const Staged2Plan& s = staged2_shape_of(plan);
     Staged2Args a = staged2_args(plan, s, d_in, d_out, 4, nz);
-    // z chunks.  Tile-major order (the default, STAGE2_ORDER 1): the chunks of a tile are consecutive workgroups of one XCD, so
-    // they start together and fetch the tile's per-output plan -- 12 bytes per cell, 0.05 GB per chunk of the benchmark
-    // launch -- once from memory instead of once per chunk, and the chip as a whole works on eight neighbouring tile rows;
-    // chunks of one size (about STAGE2_ZPB slices).  Measured on the benchmark plan (round 2's sweeps, profiles/LAB_NOTES_r01_r02.md): bilinear
-    // 2.40 -> 2.32 ms, nearest 2.32 -> 2.21 ms, 25 slices 0.322 -> 0.303 ms.
-    // Chunk-major order (STAGE2_ORDER 0, round 1 and early round 2): all tiles of chunk 0, then chunk 1, ...; the chunks shrink
-    // towards the end of the launch so that the last workgroups are short ones (STAGE2_ZTAIL).
-    const bool tileMajor = tuning("STAGE2_ORDER", 1) == 1;
-    uint32_t zpb = (uint32_t)tuning("STAGE2_ZPB", tileMajor ? 25 : 50);
-    const uint32_t ztail = tileMajor ? 0u : (uint32_t)tuning("STAGE2_ZTAIL", 10);  // 0: chunks of one size
-    if (zpb < 1) zpb = 1;
-    const size_t mostChunks = tileMajor ? 16 : (size_t)kMaxZChunks - 6;
-    if (ceil_div(nz, (size_t)zpb) > mostChunks) zpb = (uint32_t)ceil_div(nz, mostChunks);
-    uint32_t nChunks = tileMajor ? (uint32_t)ceil_div(nz, (size_t)zpb) : 0u;
-    if (tileMajor) even_z_split(a, nz, nChunks);
-    for (uint32_t z = 0; !tileMajor && z < nz;) {
-        const uint32_t rem = (uint32_t)nz - z;
-        uint32_t size = zpb;
-        if (ztail > 0 && rem <= 2 * zpb) size = std::max(ztail, (rem + 1) / 2);
-        if (size > rem || rem - size < (ztail + 1) / 2) size = rem;
-        FA_REQUIRE(nChunks < (uint32_t)kMaxZChunks, "too many z chunks for one launch");
-        a.zStart[nChunks++] = z;
-        z += size;
-    }
-    a.zStart[nChunks] = (uint32_t)nz;
+    const dim3 grid = staged2_z_chunks(a, s, nz);
     a.flags |= (uint32_t)tuning("STAGE2_STORE", 0) << 3;  // STORE 1 plain, 2 nt, 4 sc0 nt (default: sc1 nt)
-    const dim3 grid(tileMajor ? s.gridX * nChunks : s.gridX, tileMajor ? 1u : nChunks, 1);
     switch (plan.kind) {
     case PlanKind::Nearest: launch_shape<1>(s, a, grid, stream); break;
     case PlanKind::Bilinear: launch_shape<2>(s, a, grid, stream); break;

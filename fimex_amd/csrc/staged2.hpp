@@ -108,5 +108,45 @@ inline void even_z_split(Staged2Args& a, size_t nz, uint32_t n)
     a.nZChunks = n;
 }
 
+// the workgroup shape a float launch runs: the plan's choice (fimex_amd_regrid_plan_tune_device), or STAGE2_USE_ALT 0 / 1 in the
+// tuning build
+inline const Staged2Plan& staged2_shape_of(const fimex_amd_regrid_plan& plan)
+{
+    const int forced = tuning("STAGE2_USE_ALT", -1);
+    const bool alt = plan.staged2Alt.valid && (forced >= 0 ? forced == 1 : plan.useAlt != 0);
+    return alt ? plan.staged2Alt : plan.staged2;
+}
+
+// The z chunks of a float launch of nz slices (or pairs of slices) through shape `s`, written into `a`; returns the grid.
+// Tile-major order (the default, STAGE2_ORDER 1): the chunks of a tile are consecutive workgroups of one XCD, so
+// they start together and fetch the tile's per-output plan -- 12 bytes per cell, 0.05 GB per chunk of the benchmark
+// launch -- once from memory instead of once per chunk, and the chip as a whole works on eight neighbouring tile rows;
+// chunks of one size (about STAGE2_ZPB slices).  Measured on the benchmark plan (round 2's sweeps, profiles/LAB_NOTES_r01_r02.md): bilinear
+// 2.40 -> 2.32 ms, nearest 2.32 -> 2.21 ms, 25 slices 0.322 -> 0.303 ms.
+// Chunk-major order (STAGE2_ORDER 0, round 1 and early round 2): all tiles of chunk 0, then chunk 1, ...; the chunks shrink
+// towards the end of the launch so that the last workgroups are short ones (STAGE2_ZTAIL).
+inline dim3 staged2_z_chunks(Staged2Args& a, const Staged2Plan& s, size_t nz)
+{
+    const bool tileMajor = tuning("STAGE2_ORDER", 1) == 1;
+    uint32_t zpb = (uint32_t)tuning("STAGE2_ZPB", tileMajor ? 25 : 50);
+    const uint32_t ztail = tileMajor ? 0u : (uint32_t)tuning("STAGE2_ZTAIL", 10);  // 0: chunks of one size
+    if (zpb < 1) zpb = 1;
+    const size_t mostChunks = tileMajor ? 16 : (size_t)kMaxZChunks - 6;
+    if (ceil_div(nz, (size_t)zpb) > mostChunks) zpb = (uint32_t)ceil_div(nz, mostChunks);
+    uint32_t nChunks = tileMajor ? (uint32_t)ceil_div(nz, (size_t)zpb) : 0u;
+    if (tileMajor) even_z_split(a, nz, nChunks);
+    for (uint32_t z = 0; !tileMajor && z < nz;) {
+        const uint32_t rem = (uint32_t)nz - z;
+        uint32_t size = zpb;
+        if (ztail > 0 && rem <= 2 * zpb) size = std::max(ztail, (rem + 1) / 2);
+        if (size > rem || rem - size < (ztail + 1) / 2) size = rem;
+        FA_REQUIRE(nChunks < (uint32_t)kMaxZChunks, "too many z chunks for one launch");
+        a.zStart[nChunks++] = z;
+        z += size;
+    }
+    a.zStart[nChunks] = (uint32_t)nz;
+    return dim3(tileMajor ? s.gridX * nChunks : s.gridX, tileMajor ? 1u : nChunks, 1);
+}
+
 }  // namespace
 }  // namespace fimex_amd

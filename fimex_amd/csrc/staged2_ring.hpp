@@ -1,4 +1,5 @@
-// The shell of the second staged form's kernels (staged2.hip: float slices, staged2_typed.hip: stored 1- and 2-byte types): which
+// The shell of the second staged form's kernels (staged2.hip: float slices, staged2_typed.hip: stored 1- and 2-byte types,
+// staged2_vector.hip: pairs of vector components, regridded and rotated): which
 // tile and z chunk a workgroup owns, the per-lane staging list, the ring of LDS slots that slice z + 1 .. z + DEPTH - 1 stream
 // into by LDS-DMA while slice z is interpolated, and the choice of the loop copy.  The kernels keep what differs: element size,
 // per-lane plan layout, stencil reads and conversions, result stores.
@@ -71,6 +72,29 @@ struct SliceRing {
     uint32_t un;          // DMA instructions per lane and slice
     uint32_t gOff[KMAX];  // chunk c = threadIdx.x + j * NT of the tile's list: byte offset of its 16 bytes inside a source slice
     uint32_t slotChunks, slotFloats, waveChunk;
+    const char* inBaseV = nullptr;  // pairs only (run_pairs): the second component's source
+
+    // The ring of a component pair (staged2_vector.hip): float slices, [z0, z1) counts pairs, and the ring walks the 2 * (z1 - z0)
+    // logical slices u(z0), v(z0), u(z0 + 1), ... -- logical slice l is slice z0 + l / 2 of `a.in` (l even) or of `inV` (l odd).
+    __device__ __forceinline__ SliceRing(const Staged2Args& a, const StagedTile& T, uint32_t z0_, uint32_t z1_, const float* inV)
+        : inBase(reinterpret_cast<const char*>(a.in)), outBase(reinterpret_cast<char*>(a.out)), inBytes(a.inBytes),
+          outBytes(a.nOut * 4u), inRecords((kTuningBuild && (a.flags & 1)) ? 0u : a.inBytes),
+          outRecords((kTuningBuild && (a.flags & 2)) ? 0u : a.nOut * 4u), z0(z0_), z1(z1_), un((T.nChunks + NT - 1) / NT),
+          slotChunks(a.slotChunks), slotFloats(a.slotChunks * 4u), waveChunk((threadIdx.x / kWave) * kWave),
+          inBaseV(reinterpret_cast<const char*>(inV))
+    {
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) {
+            const uint32_t c = threadIdx.x + j * NT;
+            gOff[j] = (c < T.nChunks) ? a.chunkOff[T.chunkBase + c] * 4u : 0xFFFFFFFFu;
+        }
+        for (uint32_t l = 0; l + 1 < (uint32_t)DEPTH && l < 2 * (z1 - z0); ++l) {
+            const rsrc_t rs = in_pair(l);
+#pragma unroll
+            for (int j = 0; j < KMAX; ++j)
+                if ((uint32_t)j < un) dma16(rs, dma_dst(l, j), gOff[j]);
+        }
+    }
 
     __device__ __forceinline__ SliceRing(const Staged2Args& a, const StagedTile& T, uint32_t z0_, uint32_t z1_, uint32_t elemBytes)
         : inBase(reinterpret_cast<const char*>(a.in)), outBase(reinterpret_cast<char*>(a.out)), inBytes(a.inBytes),
@@ -93,6 +117,11 @@ struct SliceRing {
 
     __device__ __forceinline__ rsrc_t in(uint32_t z) const { return make_rsrc(inBase + (size_t)z * inBytes, inRecords); }
     __device__ __forceinline__ rsrc_t out(uint32_t z) const { return make_rsrc(outBase + (size_t)z * outBytes, outRecords); }
+    // logical slice l of a pair ring
+    __device__ __forceinline__ rsrc_t in_pair(uint32_t l) const
+    {
+        return make_rsrc(((l & 1u) ? inBaseV : inBase) + (size_t)(z0 + l / 2u) * inBytes, inRecords);
+    }
     // for the loops that do not go through the ring (gather tiles)
     __device__ __forceinline__ rsrc_t in_uniform(uint32_t z) const { return make_rsrc(uniform(inBase + (size_t)z * inBytes), inRecords); }
     __device__ __forceinline__ rsrc_t out_uniform(uint32_t z) const { return make_rsrc(uniform(outBase + (size_t)z * outBytes), outRecords); }
@@ -141,6 +170,61 @@ struct SliceRing {
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             slot = (slot + 1 == (uint32_t)DEPTH) ? 0 : slot + 1;
+        }
+    }
+
+    // s_waitcnt vmcnt(N) lgkmcnt(0): a u step keeps what it read from LDS in registers and stores nothing, so nothing else makes
+    // sure that its LDS reads have returned before the barrier that releases the slot to the next DMA
+    template <int N>
+    __device__ __forceinline__ static void wait_vmcnt_and_lds()
+    {
+        static_assert(N >= 0 && N < 64, "vmcnt is a 6-bit counter");
+        __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (0x7 << 4));
+        asm volatile("" ::: "memory");
+    }
+
+    // run() for a pair ring (see the pair constructor), one trip per pair with its u step and its v step written out, so that
+    // every wait keeps an immediate.  uBody(slot) interpolates the u slice into registers and issues no memory instruction that
+    // counts in vmcnt; vBody(z, slot) interpolates the v slice, rotates and issues exactly 2 * PER stores.  Logical slice l lies in
+    // slot l % DEPTH.  With S(l) the stores of logical step l (0 on a u step, 2 * PER on a v step), this was issued behind the DMA
+    // of logical slice l + 1 when step l ends and may stay in flight, by run()'s own argument:
+    //   DEPTH 2  that DMA is issued in step l itself, ahead of the step's stores: S(l), 0 after a u step, 2 * PER after a v step;
+    //   DEPTH 3  it is issued in step l - 1, then come S(l - 1), the DMA of slice l + 2 (UN instructions) and S(l); one of two
+    //            consecutive steps is a v step: UN + 2 * PER after either;
+    //   tail     the steps that fetch nothing more (DEPTH 3: both steps of the last pair; DEPTH 2: its v step -- the u step still
+    //            fetches the pair's own v slice) leave only their own stores outstanding, 0 and 2 * PER.
+    template <int UN, int PER, class UBody, class VBody>
+    __device__ __forceinline__ void run_pairs(UBody&& uBody, VBody&& vBody) const
+    {
+        static_assert(DEPTH == 2 || DEPTH == 3, "the slots of a pair's steps are written out for these depths");
+        extern __shared__ __attribute__((aligned(16))) float smem[];
+        auto fetch = [&](uint32_t l, uint32_t sl) __attribute__((always_inline)) {
+            const rsrc_t rs = in_pair(l);
+#pragma unroll
+            for (int j = 0; j < UN; ++j) dma16(rs, dma_dst(sl, j), gOff[j]);
+        };
+        auto next = [](uint32_t sl) { return sl + 1 == (uint32_t)DEPTH ? 0u : sl + 1; };
+        const uint32_t n = z1 - z0;
+        uint32_t slotU = 0;
+        for (uint32_t p = 0; p < n; ++p) {
+            const bool more = p + 1 < n;
+            const uint32_t slotV = next(slotU), slotN = next(slotV);  // DEPTH 2: slotN is slotU
+            // u step, logical slice 2p
+            if (DEPTH == 2) fetch(2 * p + 1, slotV);    // into the slot the v slice of pair p - 1 has left
+            else if (more) fetch(2 * p + 2, slotN);
+            uBody(reinterpret_cast<const char*>(smem + slotU * slotFloats));
+            if (DEPTH == 3 && more) wait_vmcnt_and_lds<UN + 2 * PER>();
+            else wait_vmcnt_and_lds<0>();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            // v step, logical slice 2p + 1
+            if (more) fetch(2 * p + DEPTH, slotU);  // into the slot the u slice has just left
+            vBody(z0 + p, reinterpret_cast<const char*>(smem + slotV * slotFloats));
+            if (more) wait_vmcnt<(DEPTH - 2) * UN + 2 * PER>();
+            else wait_vmcnt<2 * PER>();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            slotU = DEPTH == 2 ? slotU : slotN;
         }
     }
 };

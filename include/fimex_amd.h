@@ -229,6 +229,16 @@ int fimex_amd_vector_reproject_values_device(const fimex_amd_vector_plan* plan, 
  *  mifi_vector_reproject_direction_by_matrix_f (src/interpolation.c:814-835); degrees, in place. */
 int fimex_amd_vector_reproject_direction_host(const fimex_amd_vector_plan* plan, float* angles, size_t size);
 int fimex_amd_vector_reproject_direction_device(const fimex_amd_vector_plan* plan, float* d_angles, size_t oz, void* stream);
+/** CDMInterpolator::getDataSlice for an x/y vector pair (src/CDMInterpolator.cc:259-277):
+ *  interpolateValues on both components, then CachedVectorReprojection::reprojectValues, in one call.
+ *  d_u, d_v: [nz][inY][inX]; d_uOut, d_vOut: [nz][outY][outX]; none of the four may overlap another.
+ *  The plan is a backward one, the vector plan has the plan's output grid and lives on the plan's device.
+ *  *path (NULL allowed): 1 the fused kernel ran (nearest and bilinear plans with an LDS-staged form, batches of four pairs
+ *  and more), 0 the three existing launches (regrid_apply on u and on v, vector_reproject_values); the same bits either way.
+ *  The *_host form is declared in fimex_amd_vector_regrid_host.h. */
+int fimex_amd_regrid_apply_vector_device(const fimex_amd_regrid_plan* plan, const fimex_amd_vector_plan* vec,
+                                         const float* d_u, const float* d_v, size_t nz,
+                                         float* d_uOut, float* d_vOut, void* stream, int* path);
 
 /* ------------------------------------------------------ 2-D fill processes */
 /*
