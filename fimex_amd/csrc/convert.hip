@@ -5,6 +5,7 @@
 #include "plan.hpp"
 #include "typed_convert.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <string>
 #include <type_traits>
@@ -67,12 +68,18 @@ __global__ void __launch_bounds__(kBlock) replace_scalar_kernel(float* __restric
     }
 }
 
+// workgroups of a striding launch that wants `want` of them: capped, the kernels cover the rest with their grid-stride loops
+uint32_t capped_blocks(size_t want)
+{
+    const size_t cap = (size_t)std::max(1, tuning("CONVERT_MAX_BLOCKS", 256 * 8));
+    return (uint32_t)(want < cap ? (want ? want : 1) : cap);
+}
+
 template <bool TO_NAN>
 void launch_replace(float* d, size_t n, float bad, hipStream_t stream)
 {
     if (n == 0 || bad != bad) return;  // a NaN fill value leaves the data untouched (:1776, :1786)
-    const size_t groups = ceil_div(n, (size_t)4 * kBlock);
-    const uint32_t blocks = (uint32_t)(groups < 256 * 8 ? (groups ? groups : 1) : 256 * 8);
+    const uint32_t blocks = capped_blocks(ceil_div(n, (size_t)4 * kBlock));
     if (reinterpret_cast<uintptr_t>(d) % 16 == 0) replace_kernel<TO_NAN><<<blocks, kBlock, 0, stream>>>(d, n, bad);
     else replace_scalar_kernel<TO_NAN><<<blocks, kBlock, 0, stream>>>(d, n, bad);
     FA_HIP(hipGetLastError());
@@ -126,11 +133,7 @@ __global__ void __launch_bounds__(kBlock) from_float_kernel(const float* __restr
     }
 }
 
-uint32_t stream_blocks(size_t n)
-{
-    const size_t groups = ceil_div(n, (size_t)4 * kBlock);
-    return (uint32_t)(groups < 256 * 8 ? (groups ? groups : 1) : 256 * 8);
-}
+uint32_t stream_blocks(size_t n) { return capped_blocks(ceil_div(n, (size_t)4 * kBlock)); }
 
 template <typename T>
 void launch_to_float_t(const void* d_in, size_t n, double badValue, float* d_out, hipStream_t stream)
@@ -369,9 +372,7 @@ void launch_points2position(double* d_points, size_t n, const double* axis, int 
     DeviceArray<double> d_axis((size_t)num);
     FA_HIP(hipMemcpyAsync(d_axis.get(), axis, (size_t)num * sizeof(double), hipMemcpyHostToDevice, stream));
     a.axis = d_axis.get();
-    const size_t want = ceil_div(n, kBlock);
-    const uint32_t blocks = (uint32_t)(want < 256 * 8 ? want : 256 * 8);
-    points2position_kernel<<<blocks, kBlock, 0, stream>>>(a);
+    points2position_kernel<<<capped_blocks(ceil_div(n, kBlock)), kBlock, 0, stream>>>(a);
     FA_HIP(hipGetLastError());
     FA_HIP(hipStreamSynchronize(stream));  // d_axis is released on return
 }

@@ -18,6 +18,7 @@
 
 #include <rocprim/rocprim.hpp>
 
+#include <algorithm>
 #include <cmath>
 #include <vector>
 
@@ -182,8 +183,8 @@ __global__ void __launch_bounds__(kBlock) grid_distance_kernel(const double* __r
 
 uint32_t blocks_for(size_t n)
 {
-    const size_t want = ceil_div(n, (size_t)kBlock);
-    return (uint32_t)(want < 256 * 8 ? (want ? want : 1) : 256 * 8);
+    const size_t want = ceil_div(n, (size_t)kBlock), cap = (size_t)std::max(1, tuning("COORD_MAX_BLOCKS", 256 * 8));
+    return (uint32_t)(want < cap ? (want ? want : 1) : cap);
 }
 
 struct SearchIndex {

@@ -15,6 +15,7 @@
 // longitudes as pj_transform does.
 #include "extract.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <map>
@@ -1421,8 +1422,8 @@ __global__ void __launch_bounds__(kBlock) vector_matrix_kernel(ProjParams in, Pr
 
 uint32_t point_blocks(size_t n)
 {
-    const size_t want = ceil_div(n, (size_t)kBlock);
-    return (uint32_t)(want < 256 * 8 ? (want ? want : 1) : 256 * 8);
+    const size_t want = ceil_div(n, (size_t)kBlock), cap = (size_t)std::max(1, tuning("PROJECT_MAX_BLOCKS", 256 * 8));
+    return (uint32_t)(want < cap ? (want ? want : 1) : cap);
 }
 
 }  // namespace

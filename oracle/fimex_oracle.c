@@ -799,8 +799,10 @@ int orc_get_values_linear_d(const double* A, const double* B, double* out, size_
 }
 
 /* -------------------------------------- coordinate-based nearest neighbour plans (n3) */
-/* getGridDistance, src/CDMInterpolator.cc:1069-1141 */
-double orc_get_grid_distance(const double* lonVals, const double* latVals, size_t orgX, size_t orgY)
+/* getGridDistance, src/CDMInterpolator.cc:1069-1141.  *anySample: whether a sampled cell had defined coordinates (the reference
+ * takes min_element of an empty vector otherwise).  A grid of one cell has a sample but no other cell: the sample stays at -2
+ * and acos(-2) is NaN there as here. */
+static double orc_grid_distance_sampled(const double* lonVals, const double* latVals, size_t orgX, size_t orgY, int* anySample)
 {
     const size_t n = orgX * orgY;
     size_t steps, stepSize;
@@ -823,11 +825,18 @@ double orc_get_grid_distance(const double* lonVals, const double* latVals, size_
         if (min_cos_d < minOfMax) minOfMax = min_cos_d; /* min_element of the samples :1136 */
         any = 1;
     }
+    *anySample = any;
     if (!any) return nan("");
     double d = acos(minOfMax);
     d *= 1.414;
     if (d > ORC_PI) d = ORC_PI;
     return d;
+}
+
+double orc_get_grid_distance(const double* lonVals, const double* latVals, size_t orgX, size_t orgY)
+{
+    int any = 0;
+    return orc_grid_distance_sampled(lonVals, latVals, orgX, orgY, &any);
 }
 
 typedef struct { double lat, lon, x, y; } orc_ll_point;
@@ -842,8 +851,10 @@ static int orc_ll_cmp(const void* a, const void* b)
  * of cells with equal latitude is unspecified in both.) */
 int orc_fast_translate_points(double* pointsX, double* pointsY, size_t nPoints, const double* lonVals, const double* latVals, size_t orgX, size_t orgY)
 {
-    const double max_grid_d = orc_get_grid_distance(lonVals, latVals, orgX, orgY);
-    if (isnan(max_grid_d)) return ORC_ERROR;
+    int anySample = 0;
+    const double max_grid_d = orc_grid_distance_sampled(lonVals, latVals, orgX, orgY, &anySample);
+    if (!anySample) return ORC_ERROR;
+    /* one cell: max_grid_d is NaN (:1121), no comparison below holds and every point stays at -1, as in the reference */
     const double min_grid_cos_d = cos(max_grid_d);
     orc_ll_point* ll = (orc_ll_point*)malloc((orgX * orgY + 1) * sizeof(orc_ll_point));
     if (!ll) return ORC_ERROR;

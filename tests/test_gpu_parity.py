@@ -781,17 +781,23 @@ def test_data2interpolation_matches_oracle(fa, code, n, off):
         assert cases.same(got, want), cases.describe_mismatch(got, want)
 
 
-@pytest.mark.parametrize("code", sorted(oracle.CDM_DTYPES))
-@pytest.mark.parametrize("n,off", [(100003, 0), (100001, 1), (7, 0)])
-def test_interpolation2data_matches_oracle(fa, code, n, off):
-    import torch
-    dt = oracle.CDM_DTYPES[code]
-    rng = np.random.default_rng(code * 7 + n)
+def _float_field(n, off, seed):
+    """n + off floats over many magnitudes with NaN, exact halves from element off on, and -0.0 at the end."""
+    rng = np.random.default_rng(seed)
     f = (rng.normal(0, 1, n + off) * 10.0 ** rng.integers(-3, 6, n + off)).astype(np.float32)
     f[rng.choice(n, n // 20 + 1, replace=False)] = np.nan
     half = rng.integers(-300, 300, n // 10 + 1).astype(np.float32) + np.float32(0.5)  # exact ties: half away from zero
     f[off:off + half.size] = half[:f.size - off]
     f[-1] = -0.0
+    return f
+
+
+@pytest.mark.parametrize("code", sorted(oracle.CDM_DTYPES))
+@pytest.mark.parametrize("n,off", [(100003, 0), (100001, 1), (7, 0)])
+def test_interpolation2data_matches_oracle(fa, code, n, off):
+    import torch
+    dt = oracle.CDM_DTYPES[code]
+    f = _float_field(n, off, seed=code * 7 + n)
     bad = 77.0
     t = torch.from_numpy(f).cuda()
     out = torch.zeros((n + 4) * np.dtype(dt).itemsize, dtype=torch.uint8, device="cuda")

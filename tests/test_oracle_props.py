@@ -371,6 +371,155 @@ def test_flann_translate_is_the_closest_cell_within_max_dist():
     assert ((px[inside] == best[inside] % 50) & (py[inside] == best[inside] // 50)).mean() > 0.999
 
 
+# Inputs on which a search over cubes of unit vectors and a walk along sorted latitudes could disagree; tests/test_gpu_capped_grids.py
+# runs the library on the same inputs.  Each: name, lon / lat of the source [ny][nx] (rad), query lon / lat (rad), maxDist (m) of the
+# kd-tree method, and whether the COORD_NN method is run on it as well.
+def _dateline_grid():
+    """60 x 45 cells over 170 .. 190 E, 50 .. 65 N, longitudes stored wrapped into (-pi, pi]."""
+    rng = np.random.default_rng(11)
+    i, j = np.meshgrid(np.arange(60), np.arange(45))
+    lon = 170.0 + (i + 0.3 * rng.uniform(-1, 1, i.shape)) * (20.0 / 59) + 0.02 * j
+    lat = 50.0 + (j + 0.3 * rng.uniform(-1, 1, i.shape)) * (15.0 / 44) + 0.01 * i
+    lon = np.radians(lon)
+    return np.where(lon > np.pi, lon - 2 * np.pi, lon), np.radians(lat)
+
+
+def _polar_cap(south=False):
+    """40 rings x 72 longitudes from 85 degrees to the pole: a ring at 89.9, one at 89.95 of which one cell is the pole itself."""
+    rings = np.concatenate([np.linspace(85.0, 89.8, 38), [89.9, 89.95]])
+    lon = np.radians(np.tile(-180.0 + 5.0 * np.arange(72), (40, 1)) + 0.7 * np.arange(40)[:, None])  # every ring turned a little further
+    lon = np.where(lon > np.pi, lon - 2 * np.pi, lon)
+    lat = np.radians(np.tile(rings[:, None], (1, 72)))
+    lat[39, 0] = np.pi / 2
+    return lon, (-lat if south else lat)
+
+
+def _cap_queries(n, seed, south=False):
+    """Uniform on the cap within 6 degrees of the pole."""
+    rng = np.random.default_rng(seed)
+    colat = np.arccos(rng.uniform(np.cos(np.radians(6.0)), 1.0, n))
+    lat = np.pi / 2 - colat
+    lat[:4] = [np.pi / 2, np.radians(89.9), np.radians(89.99), np.radians(85.0)]
+    return rng.uniform(-np.pi, np.pi, n), (-lat if south else lat)
+
+
+def _global_grid():
+    """2.5 degrees, 144 x 73, longitudes 0 .. 357.5, both pole rows (144 coincident cells each)."""
+    lon, lat = np.meshgrid(np.radians(2.5 * np.arange(144)), np.radians(-90.0 + 2.5 * np.arange(73)))
+    return lon, lat
+
+
+def _sphere_queries(n, seed):
+    rng = np.random.default_rng(seed)
+    return rng.uniform(-np.pi, np.pi, n), np.arcsin(rng.uniform(-1, 1, n))
+
+
+def _displaced(lon, lat, maxDist, seed):
+    """The source coordinates themselves, then the same moved by up to 1.5 * maxDist (m) in random directions."""
+    rng = np.random.default_rng(seed)
+    lo, la = lon.ravel(), lat.ravel()
+    r = 1.5 * (maxDist / 6371000.0) * rng.uniform(0, 1, lo.size)
+    phi = rng.uniform(0, 2 * np.pi, lo.size)
+    return np.concatenate([lo, lo + r * np.sin(phi) / np.cos(la)]), np.concatenate([la, la + r * np.cos(phi)])
+
+
+def coord_search_inputs():
+    rng = np.random.default_rng(21)
+    out = []
+    lon, lat = _dateline_grid()
+    qlon, qlat = np.radians(rng.uniform(168.0, 192.0, 3000)), np.radians(rng.uniform(48.5, 66.5, 3000))
+    out.append(("dateline_queries_wrapped", lon, lat, np.where(qlon > np.pi, qlon - 2 * np.pi, qlon), qlat, 25000.0, True))
+    out.append(("dateline_queries_0_2pi", lon, lat, qlon, qlat, 25000.0, True))
+    for south in (False, True):
+        lon, lat = _polar_cap(south)
+        qlon, qlat = _cap_queries(3000, 31, south)
+        out.append(("south_cap" if south else "north_cap", lon, lat, qlon, qlat, 10000.0, True))
+    lon, lat = _global_grid()
+    qlon, qlat = _sphere_queries(3000, 41)
+    out.append(("global_2.5", lon, lat, qlon, qlat, 300000.0, True))
+    for nx, ny in ((25, 40), (77, 13)):  # 1000 and 1001 cells: the sampling rule of getGridDistance changes at n > 1000
+        lon, lat = _curvilinear_grid(nx, ny, seed=nx, nan=3)
+        qlon = rng.uniform(np.nanmin(lon) - 0.004, np.nanmax(lon) + 0.004, 3000); qlat = rng.uniform(lat.min() - 0.004, lat.max() + 0.004, 3000)
+        out.append(("cells_%d" % (nx * ny), lon, lat, qlon, qlat, 3000.0, True))
+    lon, lat = _curvilinear_grid(64, 64, seed=5, jitter=0.2)
+    for maxDist in (1.0, 13.0):  # 2 / (maxDist / R) is above and below 2^20 cubes per axis (12.15 m)
+        qlon, qlat = _displaced(lon, lat, maxDist, seed=int(maxDist))
+        out.append(("kd_%dm" % maxDist, lon, lat, qlon, qlat, maxDist, False))
+    return out
+
+
+def _xyz(lo, la):
+    return np.stack([np.cos(la) * np.cos(lo), np.cos(la) * np.sin(lo), np.sin(la)], -1)
+
+
+def _exhaustive(qlon, qlat, lon, lat, kd):
+    """Best cell per query over all cells and its measure: largest cos_d (COORD_NN), smallest squared chord (COORD_NN_KD)."""
+    best, val = np.empty(qlon.size, np.int64), np.empty(qlon.size)
+    lo, la = lon.ravel(), lat.ravel()
+    for s in range(0, qlon.size, 500):
+        q = slice(s, s + 500)
+        if kd:
+            m = ((_xyz(qlon[q], qlat[q])[:, None, :] - _xyz(lo, la)[None]) ** 2).sum(-1)
+            m = np.where(np.isnan(m), 9, m)
+            best[q], val[q] = m.argmin(axis=1), m.min(axis=1)
+        else:
+            m = _great_circle_cos(qlon[q, None], qlat[q, None], lo[None], la[None])
+            m = np.where(np.isnan(m), -2, m)
+            best[q], val[q] = m.argmax(axis=1), m.max(axis=1)
+    return best, val
+
+
+@pytest.mark.parametrize("case", coord_search_inputs(), ids=lambda c: c[0])
+def test_coord_search_inputs_hold_what_they_are_meant_to_and_the_oracle_stays_within_the_tie_cap(case):
+    """The GPU tests allow the library to differ from the oracle on fewer than 2 % of the queries, and only between equidistant
+    cells.  That is a condition on the inputs: here the oracle itself differs from numpy's argmax / argmin over all cells on
+    fewer than 2 % of them (coincident cells at the poles, libm against numpy in the last bit), and every input has matches
+    and non-matches (the global grid: matches only) and the geometry it is named after."""
+    name, lon, lat, qlon, qlat, maxDist, nn = case
+    nx = lon.shape[1]
+    for kd in (True, False) if nn else (True,):
+        if kd:
+            px, py = oracle.flann_translate_points(maxDist, qlon, qlat, lon, lat)
+            none, (best, val) = -1000, _exhaustive(qlon, qlat, lon, lat, True)
+            inside = val < (maxDist / 6371000.0) ** 2
+        else:
+            px, py = oracle.fast_translate_points(qlon, qlat, lon, lat)
+            none, (best, val) = -1, _exhaustive(qlon, qlat, lon, lat, False)
+            inside = val > np.cos(oracle.grid_distance(lon, lat))
+        if name.startswith("global"):
+            assert inside.all()   # no point of the sphere is further than 197 km from a cell of this grid
+        else:
+            assert inside.mean() > 0.1 and (~inside).mean() > 0.1, (name, kd, inside.mean())
+        differ = np.where(inside, (px != best % nx) | (py != best // nx), (px != none) | (py != none))
+        assert differ.mean() < 0.02, (name, kd, differ.mean())
+    if name.startswith("dateline"):
+        assert (lon > 0).any() and (lon < 0).any() and np.abs(lon).min() > 2.9          # stored on both sides of the seam
+        assert (np.cos(qlon) < 0).all() and (np.sin(qlon) > 0).any() and (np.sin(qlon) < 0).any()
+        assert (qlon > np.pi).any() == name.endswith("0_2pi")
+    if name.endswith("cap"):
+        assert (np.abs(lat) == np.pi / 2).sum() == 1 and np.isclose(np.degrees(np.abs(lat)), 89.9).any()
+        assert (np.abs(qlat) == np.pi / 2).any() and (np.sign(lat) == np.sign(lat[0, 0])).all()
+    if name.startswith("global"):
+        assert (lat == np.pi / 2).sum() == 144 and (lat == -np.pi / 2).sum() == 144 and (qlat < -1).any() and (qlat > 1).any()
+    if name.startswith("cells"):
+        assert lon.size == int(name[6:]) and lon.size in (1000, 1001)
+    if name.startswith("kd"):
+        g = np.floor(2.0 / (maxDist / 6371000.0))
+        assert (g > 2 ** 20) == (maxDist == 1.0)   # the cube grid at its cap, and just below it
+
+
+def test_fast_translate_on_one_cell_follows_the_reference():
+    """src/CDMInterpolator.cc:1121-1123: the only sample keeps min_cos_d = -2, acos(-2) is NaN, no comparison with it holds and every
+    point comes back -1 -- also the point that is the cell.  The kd-tree method has no such rule and finds the cell."""
+    lon, lat = np.array([[0.2]]), np.array([[1.0]])
+    qlon, qlat = np.array([0.2, 0.2001, 3.0]), np.array([1.0, 1.0001, -1.0])
+    assert np.isnan(oracle.grid_distance(lon, lat))
+    px, py = oracle.fast_translate_points(qlon, qlat, lon, lat)
+    assert np.all(px == -1) and np.all(py == -1)
+    kx, ky = oracle.flann_translate_points(5000.0, qlon, qlat, lon, lat)
+    assert kx.tolist() == [0, 0, -1000] and ky.tolist() == [0, 0, -1000]
+
+
 def _round_fraction_to_f32(q):
     """Correctly rounded (nearest, ties to even) float32 of an exact rational."""
     from fractions import Fraction
