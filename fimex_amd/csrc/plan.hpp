@@ -290,7 +290,7 @@ void launch_overlay(const float* d_top, const float* d_base, float* d_out, size_
 void launch_merge_fused(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream);
 void launch_merge_chain(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream);
 
-// projection.hip: pj_transform-level plan building on the device
+// projection.hip: pj_transform-level plan building on the device (strings: projection_parse.hip, point math: proj_math.hpp)
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);
 void launch_project_axes(const char* projIn, const char* projOut, const double* h_xAxis, const double* h_yAxis, size_t ix, size_t iy,
                          double* d_outX, double* d_outY, hipStream_t stream);

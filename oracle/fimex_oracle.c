@@ -28,7 +28,7 @@
  *     unspecified there; LONG_MIN (glibc, x86-64) is kept, then truncated to int
  *     as MetNoFimex::round does (include/fimex/Utils.h:72-75).
  *  D7 (not in this file: tests/test_oracle_kats.py _rotation_matrix_field and
- *     fimex_amd/csrc/projection.hip mesh_delta) the rotation matrix's delta
+ *     fimex_amd/csrc/proj_math.hpp mesh_delta) the rotation matrix's delta
  *     averages two probes of in_x_field; the second, cell (ox/2+1, oy/2+1), is
  *     past the ox*oy mesh when oy == 2, or ox == 2 and oy <= 4, and the
  *     reference reads beyond the field (src/interpolation.c:469, :494).  There

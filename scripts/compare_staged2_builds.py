@@ -8,19 +8,15 @@ alternate, one fresh process per side and round, each process runs every case: b
 bicubic in float arithmetic on 200 float slices, bilinear on int16 and nearest on uint8 on 200 slices, bilinear on 25 slices.
 Per case and round the minimum of three timed launches counts, then the median over the rounds.  Margin: new median - parent
 median <= the parent's own (max - min) over its rounds.  A sha256 of the output bytes per case must be the same on both sides in
-every round.  The driver stops at the first process that does not end normally.
+every round.  The driver (compare_builds.py) stops at the first process that does not end normally.
 """
-import argparse, hashlib, json, os, statistics, subprocess, sys
+import argparse, hashlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+import compare_builds  # beside this script
 
 ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-ap.add_argument("--parent", help="directory with the other build's libfimex_amd.so")
-ap.add_argument("--rounds", type=int, default=5)
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "staged2_split_parent_vs_new.json"))
-ap.add_argument("--parent-commit", default="parent")
-ap.add_argument("--worker", action="store_true", help="one side, one round: prints a JSON line per case")
-ap.add_argument("--lib", default=None, help="worker: directory of the library to load instead of this tree's")
+compare_builds.add_arguments(ap, os.path.join(ROOT, "profiles", "staged2_split_parent_vs_new.json"))
 args = ap.parse_args()
 
 
@@ -67,41 +63,7 @@ def worker():
     floats("bicubic_float_nz200", cubic, 200)
 
 
-def driver():
-    sides = {"parent": ["--lib", os.path.abspath(args.parent)], "new": []}
-    runs = {s: {} for s in sides}  # side -> case -> list of rounds
-    for rnd in range(args.rounds):
-        for side, extra in sides.items():
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker"] + extra, capture_output=True, text=True, timeout=300)
-            if r.returncode != 0:
-                sys.exit("round %d, %s: exit %d\n%s" % (rnd, side, r.returncode, r.stderr[-2000:]))
-            for line in r.stdout.splitlines():
-                if line.startswith("{"):
-                    c = json.loads(line)
-                    runs[side].setdefault(c["case"], []).append(c)
-            print("round", rnd, side, "done", flush=True)
-    cases, ok = {}, True
-    for case in runs["new"]:
-        e = {}
-        for side in sides:
-            mins = [min(c["seconds"]) for c in runs[side][case]]
-            e[side] = {"rounds_seconds_min": mins, "rounds_seconds_all": [c["seconds"] for c in runs[side][case]], "median": statistics.median(mins),
-                       "spread": max(mins) - min(mins), "sha256": sorted({c["sha256"] for c in runs[side][case]})}
-        e["new_minus_parent"] = e["new"]["median"] - e["parent"]["median"]
-        e["within_margin"] = e["new_minus_parent"] <= e["parent"]["spread"]
-        e["same_bits"] = len(e["parent"]["sha256"]) == 1 and e["parent"]["sha256"] == e["new"]["sha256"]
-        ok = ok and e["within_margin"] and e["same_bits"]
-        cases[case] = e
-        print(case, "parent %.4f ms  new %.4f ms  margin %.4f ms  same bits %s" % (e["parent"]["median"] * 1e3, e["new"]["median"] * 1e3,
-                                                                                  e["parent"]["spread"] * 1e3, e["same_bits"]), flush=True)
-    what = ("staged regrid launches on the benchmark geometry, commit %s against this tree, alternating in one GPU call: one fresh process per "
-            "side and round runs every case; per case and round the minimum of three launches, then the median over rounds.  Margin: new median - "
-            "parent median <= parent's (max - min) over its rounds.  sha256: of the output batch's bytes after the last launch; one value on both "
-            "sides means the same bits in every round." % args.parent_commit)
-    with open(args.out, "w") as f:
-        json.dump({"what": what, "device": "MI355X", "rounds": args.rounds, "all_within_margin_and_same_bits": ok, "cases": cases}, f, indent=1)
-        f.write("\n")
-    print("all within margin and same bits:", ok, flush=True)
+WHAT = "Staged regrid launches on the benchmark geometry."
 
 
-worker() if args.worker else driver()
+worker() if args.worker else compare_builds.drive(__file__, args, WHAT)

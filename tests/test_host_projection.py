@@ -1,6 +1,6 @@
 """Method-name mapping of the C++ host mirror (mifi_string_to_interpolation_method, src/interpolation.c:60-101).
 CPU only (host_cli --method).  The map projections themselves run on the device (fimex_amd/csrc/projection.hip) and are
-checked against oracle/proj_oracle.py in tests/test_gpu_projection.py."""
+checked against oracle/proj_oracle.py in tests/test_gpu_projection.py, and on the CPU in tests/test_projection_host.py."""
 import os
 import subprocess
 
