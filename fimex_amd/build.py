@@ -23,8 +23,10 @@ STENCIL_LIB = os.path.join(HERE, "libstencil_math_host.so")  # csrc/stencil_math
 STENCIL_SHIM = os.path.join(ROOT, "tests", "stencil_math_host.hip")
 PROJECTION_LIB = os.path.join(HERE, "libprojection_host.so")  # csrc/proj_math.hpp and the string parser compiled for the CPU (tests/test_projection_host.py)
 PROJECTION_SHIM = os.path.join(ROOT, "tests", "projection_host.hip")
+FORWARD_MATH_LIB = os.path.join(HERE, "libforward_math_host.so")  # csrc/forward_math.hpp compiled for the CPU (tests/test_forward_math_host.py)
+FORWARD_MATH_SHIM = os.path.join(ROOT, "tests", "forward_math_host.hip")
 
-DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "regrid.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "forward.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
+DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "regrid.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
                   "time_accumulate.hip", "time_interpolate.hip", "quality.hip", "extract.hip", "vertical_plan.hip"]
 
 # -ffp-contract=off: the kernels reproduce the reference's IEEE arithmetic operation by operation
@@ -133,10 +135,23 @@ def build_projection_host(force=False):
     return PROJECTION_LIB
 
 
+def build_forward_math_host(force=False):
+    """The forward aggregation rules the kernels compile (csrc/forward_math.hpp), for the host only: the tests run them on the CPU."""
+    if force or _newer(FORWARD_MATH_LIB, [FORWARD_MATH_SHIM] + _headers()):
+        cmd = [_hipcc(), "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC,
+               FORWARD_MATH_SHIM, "-o", FORWARD_MATH_LIB, "-Wl,-rpath,/opt/rocm/lib"]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("forward math shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
+        if r.stderr.strip():
+            sys.stderr.write(r.stderr)
+    return FORWARD_MATH_LIB
+
+
 def clean():
     """Removes every built artefact, so that the next build starts from the sources alone."""
     shutil.rmtree(OBJ, ignore_errors=True)
-    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, STENCIL_LIB, PROJECTION_LIB, os.path.join(HERE, "host_cli.so")):
+    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, STENCIL_LIB, PROJECTION_LIB, FORWARD_MATH_LIB, os.path.join(HERE, "host_cli.so")):
         if os.path.exists(f):
             os.remove(f)
 
@@ -149,6 +164,7 @@ def build_all(force=False, jobs=4):
     host = build_host(force=force)
     build_stencil_host(force=force)
     build_projection_host(force=force)
+    build_forward_math_host(force=force)
     return lib, host
 
 

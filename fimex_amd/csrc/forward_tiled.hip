@@ -11,8 +11,9 @@
 //     push_back order, src/CachedForwardInterpolation.cc:103-112).
 // The apply kernel streams the chunks of one slice into LDS with buffer_load_dwordx4 ... lds (whole lines, every byte once), the
 // next slice's while the lanes walk their buckets through the step table (itself in LDS for the whole z chunk) and reduce in the
-// reference's order: the same additions / comparisons as forward.hip's reduce_bucket, so results stay bit-identical.
+// reference's order: the rules of forward_math.hpp (its padded step), as in every other forward kernel, so results stay bit-identical.
 // Tiles whose buckets are spread too far for LDS (a bucket across the date line, a pole) read from memory as the lane kernels do.
+#include "forward_math.hpp"
 #include "staged_common.hpp"
 #include "typed_convert.hpp"
 
@@ -41,22 +42,11 @@ constexpr uint32_t kFtGroup = 8;  // steps whose positions a lane reads with one
 // entry of (step s, lane l) in a tile's step table: groups of eight steps, lane-major inside a group
 __host__ __device__ inline size_t step_entry(uint32_t s, uint32_t lane) { return ((size_t)(s / kFtGroup) * kWave + lane) * kFtGroup + s % kFtGroup; }
 
-__device__ __forceinline__ uint32_t wave_max_u(uint32_t v)
+template <bool MAX>
+__device__ __forceinline__ int wave_extreme(int v)
 {
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ int wave_min_i(int v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, kWave));
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, kWave));
+    for (int d = 32; d > 0; d >>= 1) v = MAX ? max(v, __shfl_xor(v, d, kWave)) : min(v, __shfl_xor(v, d, kWave));
     return v;
 }
 
@@ -73,7 +63,7 @@ __global__ void __launch_bounds__(kWave) forward_tile_scan(FtGeom g, const uint3
     const bool mine = tx < g.outX && ty < g.outY;
     uint32_t b = 0, e = 0;
     if (mine) { const uint32_t t = ty * g.outX + tx; b = offsets[t]; e = offsets[t + 1]; }
-    const uint32_t maxLen = wave_max_u(e - b);
+    const uint32_t maxLen = (uint32_t)wave_extreme<true>((int)(e - b));  // a bucket holds fewer than 2^30 cells
     FtTile T = EMIT ? tiles[tile] : FtTile{0, 0, 0, maxLen};
     if (maxLen == 0) {
         if (!EMIT && lane == 0) tiles[tile] = FtTile{0, 0, 0, 0};
@@ -86,8 +76,8 @@ __global__ void __launch_bounds__(kWave) forward_tile_scan(FtGeom g, const uint3
         rmin = min(rmin, row);
         rmax = max(rmax, row);
     }
-    rmin = wave_min_i(rmin);
-    rmax = wave_max_i(rmax);
+    rmin = wave_extreme<false>(rmin);
+    rmax = wave_extreme<true>(rmax);
     const int nr = rmax - rmin + 1;
     if (nr > kFtMaxRows || maxLen > kFtMaxLen) {  // wave-uniform
         if (!EMIT && lane == 0) tiles[tile] = FtTile{0, kFtDirect, 0, maxLen};
@@ -153,49 +143,6 @@ struct FtArgs {
     size_t inLayer;
 };
 
-// One value of a bucket in scan order.  The arithmetic of forward.hip's reduce_bucket (sum / mean / max / min = KIND 0 / 1 / 3 / 4) with
-// nothing to decide per step beyond it: steps past the end of a lane's bucket read the slot's padding cell, whose value leaves the
-// result alone (NaN where NaNs are skipped or never win a comparison; -0.0 for the sums that keep NaNs: x + -0.0 == x for every x,
-// signed zeros included), and the kinds that keep undefined values know their count (the bucket's length) without counting.
-//   max / min start from -inf / +inf instead of "the first kept value": a comparison with the first value then takes it, or leaves
-//   an equal infinity -- the same value; a NaN in first place (kept by the "undef" kinds: std::max_element returns it) is looked at
-//   separately (firstNan).
-template <int KIND, bool UNDEF>
-__device__ __forceinline__ void take(float v, float& acc, uint32_t& cnt)
-{
-    if (KIND == 0 || KIND == 1) {
-        if (UNDEF) acc = acc + v;                           // std::accumulate(.., 0.f), NaNs included
-        else { const bool ok = v == v; acc = ok ? acc + v : acc; cnt += ok ? 1u : 0u; }
-    } else {
-        if (KIND == 3) acc = (acc < v) ? v : acc;            // std::max_element: the first of equal elements stays
-        else acc = (v < acc) ? v : acc;                      // std::min_element
-        if (!UNDEF) cnt += (v == v) ? 1u : 0u;
-    }
-}
-template <int KIND, bool UNDEF>
-__device__ __forceinline__ float start_value() { return (KIND == 3) ? -INFINITY : (KIND == 4) ? INFINITY : 0.f; }
-template <int KIND, bool UNDEF>
-__device__ __forceinline__ float padding_value() { return ((KIND == 0 || KIND == 1) && UNDEF) ? -0.f : undefined_f(); }
-template <int KIND, bool UNDEF>
-__device__ __forceinline__ float finish(float acc, uint32_t cnt, uint32_t len, bool firstNan)
-{
-    const uint32_t n = UNDEF ? len : cnt;
-    if (n == 0) return undefined_f();                        // empty bucket, src/CachedForwardInterpolation.cc:123-124
-    if ((KIND == 3 || KIND == 4) && UNDEF && firstNan) return undefined_f();
-    return KIND == 1 ? acc / (float)n : acc;                 // aggrMean: sum / size()
-}
-// the lane kernels' step (forward.hip reduce_bucket), for tiles that are not staged
-template <int KIND, bool UNDEF>
-__device__ __forceinline__ void take_plain(float v, float& acc, uint32_t& cnt)
-{
-    if (UNDEF || !isnan(v)) {
-        if (KIND == 0 || KIND == 1) acc = acc + v;
-        else if (KIND == 3) { if (cnt == 0 || acc < v) acc = v; }
-        else { if (cnt == 0 || v < acc) acc = v; }
-        cnt++;
-    }
-}
-
 // element of a slice as float: Data::asFloat + mifi_bad2nanf for the stored types (typed_convert.hpp)
 template <typename T>
 __device__ __forceinline__ float cell_value(T raw, float bad, bool hasBad)
@@ -212,8 +159,8 @@ __device__ __forceinline__ void store_result(T* p, float r, T fill)
 }
 
 // Slices z0 .. z1 of one tile, by one wave.  E: the slices' element type.  Stored types have no element that stands for "leaves
-// the result alone" (see take), so their steps past a bucket's end are replaced by that value after the conversion.
-template <int KIND, bool UNDEF, int G, int KMAX, typename E>
+// the result alone" (forward_math.hpp: take), so their steps past a bucket's end are replaced by that value after the conversion.
+template <Aggregate A, bool UNDEF, int G, int KMAX, typename E>
 __device__ __forceinline__ void tile_slices(const FtArgs& a, uint32_t tile, uint32_t z0, uint32_t z1)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];  // the workgroup's dynamic LDS
@@ -240,8 +187,8 @@ __device__ __forceinline__ void tile_slices(const FtArgs& a, uint32_t tile, uint
             const E* s = reinterpret_cast<const E*>(inBase + (size_t)z * sliceBytes);
             float acc = 0.f;
             uint32_t cnt = 0;
-            for (uint32_t j = b; j < e; ++j) take_plain<KIND, UNDEF>(cell_value<E>(s[a.src[j]], a.bad, hasBad), acc, cnt);
-            store_result<E>(outBase + (size_t)z * a.nOut + t, cnt == 0 ? undefined_f() : (KIND == 1 ? acc / (float)cnt : acc), fill);
+            for (uint32_t j = b; j < e; ++j) ordered_step<A, UNDEF>(cell_value<E>(s[a.src[j]], a.bad, hasBad), acc, cnt);
+            store_result<E>(outBase + (size_t)z * a.nOut + t, finish<A, UNDEF>(acc, cnt, cnt, false), fill);
         }
         return;
     }
@@ -284,7 +231,7 @@ __device__ __forceinline__ void tile_slices(const FtArgs& a, uint32_t tile, uint
     // a.slots slices per pass: all of them are asked for, then waited for, then reduced one after the other.  One by default: with
     // long buckets LDS bounds the waves of a CU (a second slot for a prefetch halved them and lost), with short ones
     // several slices per wave in flight gained nothing
-    if (lane < a.slots) smem[lane * slotFloats + a.slotChunks * 4u] = padding_value<KIND, UNDEF>();
+    if (lane < a.slots) smem[lane * slotFloats + a.slotChunks * 4u] = padding_value<A, UNDEF>();
     // every load so far has returned (the builtin, not inline assembly: the compiler's own counter tracking must see these waits, or
     // it waits for the loads of before the loop, behind the DMAs, inside the walk)
     __builtin_amdgcn_s_waitcnt(0x0070);
@@ -297,7 +244,7 @@ __device__ __forceinline__ void tile_slices(const FtArgs& a, uint32_t tile, uint
         for (uint32_t sl = 0; sl < here; ++sl) {
             const uint32_t z = zp + sl;
             const char* cur = reinterpret_cast<const char*>(&smem[sl * slotFloats]);
-            float acc = start_value<KIND, UNDEF>();
+            float acc = start_value<A, UNDEF>();
             uint32_t cnt = 0;
             // the walk, eight steps at a time: the values of group k + 1 are on their way while group k is reduced
             auto values = [&](int k, float (&v)[kFtGroup]) __attribute__((always_inline)) {
@@ -309,7 +256,7 @@ __device__ __forceinline__ void tile_slices(const FtArgs& a, uint32_t tile, uint
                 if constexpr (kTyped) {
 #pragma unroll
                     for (int i = 0; i < (int)kFtGroup; ++i)
-                        v[i] = ((uint32_t)(k * (int)kFtGroup + i) < len) ? v[i] : padding_value<KIND, UNDEF>();
+                        v[i] = ((uint32_t)(k * (int)kFtGroup + i) < len) ? v[i] : padding_value<A, UNDEF>();
                 }
             };
             float v[kFtGroup], vn[kFtGroup];
@@ -321,12 +268,12 @@ __device__ __forceinline__ void tile_slices(const FtArgs& a, uint32_t tile, uint
                 if ((uint32_t)k < walk) {  // wave-uniform
                     if (k + 1 < G) values(k + 1, vn);
 #pragma unroll
-                    for (uint32_t i = 0; i < kFtGroup; ++i) take<KIND, UNDEF>(v[i], acc, cnt);
+                    for (uint32_t i = 0; i < kFtGroup; ++i) take<A, UNDEF>(v[i], acc, cnt);
 #pragma unroll
                     for (uint32_t i = 0; i < kFtGroup; ++i) v[i] = vn[i];
                 }
             }
-            if (mine) store_result<E>(outBase + (size_t)z * a.nOut + t, finish<KIND, UNDEF>(acc, cnt, len, firstNan), fill);
+            if (mine) store_result<E>(outBase + (size_t)z * a.nOut + t, finish<A, UNDEF>(acc, cnt, len, firstNan), fill);
         }
         __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the reads of this pass are done before the next one overwrites the slots
         asm volatile("" ::: "memory");
@@ -339,54 +286,36 @@ __device__ __forceinline__ void tile_slices(const FtArgs& a, uint32_t tile, uint
 // (Measured against it: as many waves as the chip holds, each with an equal run of (tile, slice) pairs -- no last round for a few
 // tiles, but all waves of a CU then stage and walk in step, 0.66 ms against 0.57 for the dense case of DESIGN.md 6; workgroups that
 // start whenever one ends keep the phases apart.)
-template <int KIND, bool UNDEF, int G, int KMAX, typename T = float>
+template <Aggregate A, bool UNDEF, int G, int KMAX, typename T = float>
 __global__ void __launch_bounds__(kWave) forward_apply_tiled(FtArgs a)
 {
     const uint32_t perXcd = gridDim.x / kXcds;
     const uint32_t tile = (blockIdx.x % kXcds) * perXcd + blockIdx.x / kXcds;
     if (tile >= a.g.nTiles) return;
-    tile_slices<KIND, UNDEF, G, KMAX, T>(a, tile, a.zStart[blockIdx.y], a.zStart[blockIdx.y + 1]);
+    tile_slices<A, UNDEF, G, KMAX, T>(a, tile, a.zStart[blockIdx.y], a.zStart[blockIdx.y + 1]);
 }
 
 // G groups of eight steps in registers, KMAX chunks per lane and slice: the smallest form that holds the plan's longest bucket and
 // largest tile -- short buckets take few registers and many waves per SIMD, which is what hides the wait for a slice there
-template <int KIND, bool UNDEF>
+template <Aggregate A, bool UNDEF>
 void launch_tiled(const FtArgs& a, uint32_t groups, dim3 grid, size_t lds, hipStream_t stream)
 {
     const uint32_t kmax = a.slotChunks / kWave;
-    if (groups <= 2 && kmax <= 4) forward_apply_tiled<KIND, UNDEF, 2, 4><<<grid, kWave, lds, stream>>>(a);
-    else if (groups <= 4 && kmax <= 8) forward_apply_tiled<KIND, UNDEF, 4, 8><<<grid, kWave, lds, stream>>>(a);
-    else if (groups <= 8 && kmax <= 16) forward_apply_tiled<KIND, UNDEF, 8, 16><<<grid, kWave, lds, stream>>>(a);
-    else if (groups <= 16) forward_apply_tiled<KIND, UNDEF, 16, 32><<<grid, kWave, lds, stream>>>(a);
-    else forward_apply_tiled<KIND, UNDEF, 32, 32><<<grid, kWave, lds, stream>>>(a);
+    if (groups <= 2 && kmax <= 4) forward_apply_tiled<A, UNDEF, 2, 4><<<grid, kWave, lds, stream>>>(a);
+    else if (groups <= 4 && kmax <= 8) forward_apply_tiled<A, UNDEF, 4, 8><<<grid, kWave, lds, stream>>>(a);
+    else if (groups <= 8 && kmax <= 16) forward_apply_tiled<A, UNDEF, 8, 16><<<grid, kWave, lds, stream>>>(a);
+    else if (groups <= 16) forward_apply_tiled<A, UNDEF, 16, 32><<<grid, kWave, lds, stream>>>(a);
+    else forward_apply_tiled<A, UNDEF, 32, 32><<<grid, kWave, lds, stream>>>(a);
 }
 // stored types: three forms
-template <int KIND, bool UNDEF, typename T>
+template <Aggregate A, bool UNDEF, typename T>
 void launch_tiled_typed(const FtArgs& a, uint32_t groups, dim3 grid, size_t lds, hipStream_t stream)
 {
     const uint32_t kmax = a.slotChunks / kWave;
-    if (groups <= 4 && kmax <= 8) forward_apply_tiled<KIND, UNDEF, 4, 8, T><<<grid, kWave, lds, stream>>>(a);
-    else if (groups <= 16) forward_apply_tiled<KIND, UNDEF, 16, 32, T><<<grid, kWave, lds, stream>>>(a);
-    else forward_apply_tiled<KIND, UNDEF, 32, 32, T><<<grid, kWave, lds, stream>>>(a);
+    if (groups <= 4 && kmax <= 8) forward_apply_tiled<A, UNDEF, 4, 8, T><<<grid, kWave, lds, stream>>>(a);
+    else if (groups <= 16) forward_apply_tiled<A, UNDEF, 16, 32, T><<<grid, kWave, lds, stream>>>(a);
+    else forward_apply_tiled<A, UNDEF, 32, 32, T><<<grid, kWave, lds, stream>>>(a);
 }
-template <typename T>
-bool launch_tiled_typed_kind(const fimex_amd_regrid_plan& plan, const FtArgs& a, uint32_t groups, dim3 grid, size_t lds, hipStream_t stream)
-{
-    const bool u = plan.undefAggr;
-    switch (plan.aggregate) {
-    case Aggregate::Sum: u ? launch_tiled_typed<0, true, T>(a, groups, grid, lds, stream) : launch_tiled_typed<0, false, T>(a, groups, grid, lds, stream); break;
-    case Aggregate::Mean: u ? launch_tiled_typed<1, true, T>(a, groups, grid, lds, stream) : launch_tiled_typed<1, false, T>(a, groups, grid, lds, stream); break;
-    case Aggregate::Max: u ? launch_tiled_typed<3, true, T>(a, groups, grid, lds, stream) : launch_tiled_typed<3, false, T>(a, groups, grid, lds, stream); break;
-    case Aggregate::Min: u ? launch_tiled_typed<4, true, T>(a, groups, grid, lds, stream) : launch_tiled_typed<4, false, T>(a, groups, grid, lds, stream); break;
-    default: return false;
-    }
-    return true;
-}
-
-}  // namespace
-
-namespace {
-
 // The tiled form of a forward plan (after the CSR) for slices of cellBytes-byte elements: built where the buckets are long on average.
 void build_tiles(const fimex_amd_regrid_plan& plan, ForwardTiles& ft, uint32_t cellBytes, size_t& planBytes, hipStream_t stream)
 {
@@ -548,14 +477,7 @@ bool launch_forward_tiled(const fimex_amd_regrid_plan& plan, const float* d_in, 
     size_t lds = 0;
     if (!prepare_launch(plan, ft, d_in, nz, d_out, a, grid, lds)) return false;
     const uint32_t groups = ft.groups;  // of the plan's longest bucket
-    const bool u = plan.undefAggr;
-    switch (plan.aggregate) {
-    case Aggregate::Sum: u ? launch_tiled<0, true>(a, groups, grid, lds, stream) : launch_tiled<0, false>(a, groups, grid, lds, stream); break;
-    case Aggregate::Mean: u ? launch_tiled<1, true>(a, groups, grid, lds, stream) : launch_tiled<1, false>(a, groups, grid, lds, stream); break;
-    case Aggregate::Max: u ? launch_tiled<3, true>(a, groups, grid, lds, stream) : launch_tiled<3, false>(a, groups, grid, lds, stream); break;
-    case Aggregate::Min: u ? launch_tiled<4, true>(a, groups, grid, lds, stream) : launch_tiled<4, false>(a, groups, grid, lds, stream); break;
-    default: return false;
-    }
+    if (!with_aggregate(plan.aggregate, plan.undefAggr, [&](auto A, auto U) { launch_tiled<A(), U()>(a, groups, grid, lds, stream); })) return false;
     FA_HIP(hipGetLastError());
     return true;
 }
@@ -594,12 +516,15 @@ bool launch_forward_tiled_typed(const fimex_amd_regrid_plan& plan, const void* d
     a.bad = (float)badValue;
     a.hasBad = !(a.bad != a.bad);
     a.fillOut = badValue;
+    const auto typed = [&](auto t) {
+        return with_aggregate(plan.aggregate, plan.undefAggr, [&](auto A, auto U) { launch_tiled_typed<A(), U(), decltype(t)>(a, ft->groups, grid, lds, stream); });
+    };
     bool ok = false;
     switch (cdmType) {
-    case FIMEX_AMD_CDM_CHAR: ok = launch_tiled_typed_kind<signed char>(plan, a, ft->groups, grid, lds, stream); break;
-    case FIMEX_AMD_CDM_UCHAR: ok = launch_tiled_typed_kind<unsigned char>(plan, a, ft->groups, grid, lds, stream); break;
-    case FIMEX_AMD_CDM_SHORT: ok = launch_tiled_typed_kind<short>(plan, a, ft->groups, grid, lds, stream); break;
-    default: ok = launch_tiled_typed_kind<unsigned short>(plan, a, ft->groups, grid, lds, stream); break;
+    case FIMEX_AMD_CDM_CHAR: ok = typed((signed char)0); break;
+    case FIMEX_AMD_CDM_UCHAR: ok = typed((unsigned char)0); break;
+    case FIMEX_AMD_CDM_SHORT: ok = typed((short)0); break;
+    default: ok = typed((unsigned short)0); break;
     }
     FA_HIP(hipGetLastError());
     return ok;

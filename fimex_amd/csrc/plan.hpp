@@ -172,8 +172,9 @@ void launch_staged2_apply_vector(const fimex_amd_regrid_plan& plan, const fimex_
 bool launch_staged2_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                 hipStream_t stream);
 
-// forward.hip
+// forward_plan.hip
 void build_forward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
+// forward.hip (the medians of medium buckets: forward_median.hip, declared in forward.hpp)
 void launch_forward_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
 
 // forward_tiled.hip

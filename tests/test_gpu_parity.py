@@ -1045,6 +1045,35 @@ def test_forward_on_the_stored_type(fa, monkeypatch, method, dt, bad, shape, den
         assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), (fused, np.dtype(dt).name, int((got != want).sum()))
 
 
+@pytest.mark.parametrize("method", [oracle.FWD_MEAN, oracle.FWD_UNDEF_MIN])
+@pytest.mark.parametrize("dt,bad", [(np.int16, -32767.0), (np.uint8, 255.0)])
+def test_forward_on_the_stored_type_tiles_read_from_memory(fa, method, dt, bad):
+    """The stored-type forward kernel on a plan some of whose tiles cannot be staged (`special`: source cells thrown to the corners and
+    edges of the target, buckets whose cells lie far apart): those tiles walk their buckets in memory with the lane kernels' ordered
+    step.  The geometry is test_forward_tiled_mappings' (333, 377, 32, 80) with its seed: following forward_tile_scan by hand in numpy,
+    3 of its 40 occupied tiles exceed a slot's 2048 chunks with 2-byte elements and 1 with 1-byte elements; (300, 200, 50, 33)
+    stages every tile.  Against the oracle's three steps."""
+    import torch
+    inX, inY, outX, outY = 333, 377, 32, 80
+    nz = 3
+    px, py = cases.forward_positions(inX, inY, outX, outY, seed=31, density=1.3, special=True)
+    rng = np.random.default_rng(6)
+    info = np.iinfo(dt)
+    f = rng.integers(max(info.min, -3000) // 2, min(info.max, 3000) // 2 + 1, (nz, inY, inX)).astype(dt)
+    f.reshape(-1)[rng.choice(f.size, f.size // 20, replace=False)] = dt(bad)
+    code = oracle.cdm_type_of(dt)
+    want = oracle.interpolation_array2data(
+        oracle.forward_interpolate_values(method, px, py, oracle.data2interpolation_array(f, bad), inX, inY, outX, outY), code, bad)
+    plan = fa.RegridPlan(method, px, py, inX, inY, outX, outY)
+    assert plan.info()["stagedCells"] > 0, plan.info()
+    t = torch.from_numpy(f.view(np.uint8)).cuda()
+    out = torch.zeros(nz * outY * outX * np.dtype(dt).itemsize, dtype=torch.uint8, device="cuda")
+    fa.regrid_apply_typed_device(plan, t.data_ptr(), code, nz, bad, out.data_ptr())
+    torch.cuda.synchronize()
+    got = out.cpu().numpy().view(dt).reshape(want.shape)
+    assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), (np.dtype(dt).name, int((got != want).sum()))
+
+
 @pytest.mark.parametrize("dt,bad", [(np.int16, -32767.0), (np.uint8, 255.0)])
 def test_forward_on_the_stored_type_through_host_buffers(fa, dt, bad):
     """fimex_amd_regrid_slice_typed_host with a forward plan of long buckets: the streamed host pipeline hands its chunks of slices to the
