@@ -26,7 +26,7 @@ PROJECTION_SHIM = os.path.join(ROOT, "tests", "projection_host.hip")
 FORWARD_MATH_LIB = os.path.join(HERE, "libforward_math_host.so")  # csrc/forward_math.hpp compiled for the CPU (tests/test_forward_math_host.py)
 FORWARD_MATH_SHIM = os.path.join(ROOT, "tests", "forward_math_host.hip")
 
-DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "regrid.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
+DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
                   "time_accumulate.hip", "time_interpolate.hip", "quality.hip", "extract.hip", "vertical_plan.hip"]
 
 # -ffp-contract=off: the kernels reproduce the reference's IEEE arithmetic operation by operation

@@ -11,8 +11,8 @@
 // z loop; kAhead slices are in flight per lane.  Every slice has its own buffer descriptor, so a batch of any length is addressed
 // with 32-bit lane offsets (a slice holds fewer than 2^30 cells, plan.hpp).  The plan entries and the stencil arithmetic are those
 // of stencil_math.hpp.  Built with -ffp-contract=off: I + alpha * diff is a multiply and an add, as in the reference.
+#include "gather_entry.hpp"
 #include "plan.hpp"
-#include "stencil_math.hpp"
 
 #include <cmath>
 
@@ -23,20 +23,6 @@ namespace {
 constexpr int kTileX = 64, kTileY = 4;  // a wave per row
 static_assert(kTileX * kTileY == kBlock, "a tile is one workgroup");
 constexpr int kAhead = 4;               // slices whose loads are in flight together
-
-__device__ __forceinline__ float ld(rsrc_t r, uint32_t voff)
-{
-    return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff, 0, 0));
-}
-// written once and never re-read by the kernel that writes it: non-temporal (aux = 2), as the applies of regrid.hip
-__device__ __forceinline__ void st_stream(rsrc_t r, uint32_t voff, float v)
-{
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, 0, 2);
-}
-__device__ __forceinline__ void st_plain(rsrc_t r, uint32_t voff, float v)
-{
-    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), r, voff, 0, 0);
-}
 
 // ---- CDMBorderSmoothing_Linear::operator() (:41-85), split into what depends on the cell and what depends on the values.
 // size_t arithmetic that wraps, as the reference's: xmax2 = nx - bw and xmin2 = xmax2 - tw may wrap, and the comparisons decide
@@ -126,11 +112,11 @@ __global__ void __launch_bounds__(kBlock) border_smooth_kernel(const SmoothArgs 
             vo[k] = ld(make_rsrc(a.outer + (size_t)(z + k) * plane, planeBytes), cb);
         }
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, smooth_value(c, vi[k], vo[k], useOuter));
+        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, 0, smooth_value(c, vi[k], vo[k], useOuter));
     }
     for (; z < z1; ++z) {
         const float vi = ld(make_rsrc(a.inner + (size_t)z * plane, planeBytes), cb), vo = ld(make_rsrc(a.outer + (size_t)z * plane, planeBytes), cb);
-        st_plain(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, smooth_value(c, vi, vo, useOuter));
+        st_plain(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, 0, smooth_value(c, vi, vo, useOuter));
     }
 }
 
@@ -152,7 +138,8 @@ __global__ void __launch_bounds__(kBlock) overlay_kernel(const float* top, const
     }
 }
 
-// ---- one entry of a backward plan, decoded once per cell and evaluated slice by slice (stencil_math.hpp)
+// ---- a backward plan's arrays; an entry is decoded once per cell and evaluated slice by slice (gather_entry.hpp: an undefined
+// entry issues loads that are dropped and gives NaN, so the lane stays on the common path)
 struct PlanRef {
     const uint32_t* pos;
     const float *xf, *yf;
@@ -160,79 +147,13 @@ struct PlanRef {
     uint32_t ix;       // source row length
     uint32_t inBytes;  // bytes of a source slice
     size_t inLayer;    // cells of a source slice
-};
 
-// An undefined entry (kInvalidPos) is given a lane offset beyond every slice and zero strides: the buffer range check drops its
-// loads, so it reads nothing and the lane stays on the common path; the value is then replaced by NaN.
-constexpr uint32_t kDropped = 0xFFFFFFFCu;  // a slice has fewer than 2^30 cells: its bytes end below this offset
-
-template <int STENCIL>
-struct Entry;
-
-template <>
-struct Entry<1> {
-    uint32_t pb;
-    bool valid;
-    __device__ __forceinline__ Entry(const PlanRef& p, uint32_t cell)
+    template <int STENCIL>
+    __device__ __forceinline__ GatherEntry<STENCIL, float> entry(uint32_t cell) const
     {
-        const uint32_t q = p.pos[cell];
-        valid = q != kInvalidPos;
-        pb = valid ? q * 4u : kDropped;
-    }
-    __device__ __forceinline__ float value(rsrc_t rs) const
-    {
-        const float v = ld(rs, pb);
-        return valid ? v : undefined_f();
-    }
-};
-
-template <>
-struct Entry<2> {
-    uint32_t pb, dxb, dyb;
-    float xf, yf;
-    bool valid;
-    __device__ __forceinline__ Entry(const PlanRef& p, uint32_t cell)
-    {
-        const uint32_t q = p.pos[cell];
-        xf = p.xf[cell];
-        yf = p.yf[cell];
-        valid = q != kInvalidPos;
-        pb = valid ? q * 4u : kDropped;
-        dxb = (!valid || is_nn(xf)) ? 0u : 4u;  // a missing neighbour repeats the cell itself (its value is not selected)
-        dyb = (!valid || is_nn(yf)) ? 0u : p.ix * 4u;
-    }
-    __device__ __forceinline__ float value(rsrc_t rs) const
-    {
-        const float s00 = ld(rs, pb), s01 = ld(rs, pb + dxb), s10 = ld(rs, pb + dyb), s11 = ld(rs, pb + dxb + dyb);
-        const float v = bilinear_value(s00, s01, s10, s11, xf, yf);
-        return valid ? v : undefined_f();
-    }
-};
-
-template <>
-struct Entry<4> {
-    uint32_t pb, colb, rowb;  // byte steps to the next column and row of the stencil
-    bool valid;
-    double XM[4], MY[4];
-    __device__ __forceinline__ Entry(const PlanRef& p, uint32_t cell)
-    {
-        const uint32_t q = p.pos[cell];
-        valid = q != kInvalidPos;
-        pb = valid ? q * 4u : kDropped;
-        colb = valid ? 4u : 0u;
-        rowb = valid ? p.ix * 4u : 0u;
-        cubic_weights(p.xfd[cell], XM);
-        cubic_weights(p.yfd[cell], MY);
-    }
-    __device__ __forceinline__ float value(rsrc_t rs) const
-    {
-        float f[4][4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) f[i][j] = ld(rs, pb + i * rowb + j * colb);
-        const float v = bicubic_point(f, XM, MY);
-        return valid ? v : undefined_f();
+        if constexpr (STENCIL == 4) return {pos[cell], xfd[cell], yfd[cell], ix};
+        else if constexpr (STENCIL == 2) return {pos[cell], xf[cell], yf[cell], ix};
+        else return {pos[cell], 0.f, 0.f, ix};
     }
 };
 
@@ -254,7 +175,7 @@ __global__ void __launch_bounds__(kBlock) merge_smooth_kernel(const MergeSmoothA
     if (x >= a.nx || y >= a.ny) return;
     const uint32_t cell = y * a.nx + x, cb = cell * 4u;
     const SmoothClass c = smooth_class(x, y, a.nx, a.ny, a.tw, a.bw);
-    const Entry<STENCIL> e(a.oi, cell);
+    const GatherEntry<STENCIL, float> e = a.oi.entry<STENCIL>(cell);
     const bool useOuter = a.useOuter != 0;
     const size_t plane = (size_t)a.nx * a.ny;
     const uint32_t planeBytes = (uint32_t)plane * 4u;
@@ -268,12 +189,12 @@ __global__ void __launch_bounds__(kBlock) merge_smooth_kernel(const MergeSmoothA
         for (int k = 0; k < kAhead; ++k)
             vo[k] = needs_outer(c, vi[k], useOuter) ? e.value(make_rsrc(a.outer + (size_t)(z + k) * a.oi.inLayer, a.oi.inBytes)) : 0.f;
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.s + (size_t)(z + k) * plane, planeBytes), cb, smooth_value(c, vi[k], vo[k], useOuter));
+        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.s + (size_t)(z + k) * plane, planeBytes), cb, 0, smooth_value(c, vi[k], vo[k], useOuter));
     }
     for (; z < z1; ++z) {
         const float vi = ld(make_rsrc(a.inner + (size_t)z * plane, planeBytes), cb);
         const float vo = needs_outer(c, vi, useOuter) ? e.value(make_rsrc(a.outer + (size_t)z * a.oi.inLayer, a.oi.inBytes)) : 0.f;
-        st_plain(make_rsrc(a.s + (size_t)z * plane, planeBytes), cb, smooth_value(c, vi, vo, useOuter));
+        st_plain(make_rsrc(a.s + (size_t)z * plane, planeBytes), cb, 0, smooth_value(c, vi, vo, useOuter));
     }
 }
 
@@ -294,8 +215,8 @@ __global__ void __launch_bounds__(kBlock) merge_overlay_kernel(const MergeOverla
     const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
     if (x >= a.nx || y >= a.ny) return;
     const uint32_t cell = y * a.nx + x, cb = cell * 4u;
-    const Entry<ST> es(a.st, cell);
-    const Entry<OT> eo(a.ot, cell);
+    const GatherEntry<ST, float> es = a.st.entry<ST>(cell);
+    const GatherEntry<OT, float> eo = a.ot.entry<OT>(cell);
     const size_t plane = (size_t)a.nx * a.ny;
     const uint32_t planeBytes = (uint32_t)plane * 4u;
     uint32_t z = blockIdx.z * a.zPerBlock;
@@ -308,12 +229,12 @@ __global__ void __launch_bounds__(kBlock) merge_overlay_kernel(const MergeOverla
         for (int k = 0; k < kAhead; ++k)
             if (v[k] != v[k]) v[k] = eo.value(make_rsrc(a.outer + (size_t)(z + k) * a.ot.inLayer, a.ot.inBytes));
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) st_stream(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, v[k]);
+        for (int k = 0; k < kAhead; ++k) st_stream(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, 0, v[k]);
     }
     for (; z < z1; ++z) {
         float v = es.value(make_rsrc(a.s + (size_t)z * a.st.inLayer, a.st.inBytes));
         if (v != v) v = eo.value(make_rsrc(a.outer + (size_t)z * a.ot.inLayer, a.ot.inBytes));
-        st_stream(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, v);
+        st_stream(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, 0, v);
     }
 }
 

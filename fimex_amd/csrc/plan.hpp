@@ -148,10 +148,15 @@ struct fimex_amd_merge_plan {
 
 namespace fimex_amd {
 
-// regrid.hip
+// backward_plan.hip: classification, and the choice between the staged forms and the gather
 void build_backward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
 void launch_backward_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+                        hipStream_t stream);
+// gather.hip: the per-lane gather kernel on float slices and on stored types
 void launch_backward_gather(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+bool launch_typed_gather(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+                         hipStream_t stream);
 
 // staged.hip
 bool build_staged_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
@@ -198,9 +203,6 @@ void launch_get_values_linear_d(const double* A, const double* B, double* out, s
 size_t cdm_type_size(int cdmType);  // throws for types without a float form
 void launch_data2interpolation(const void* d_in, int cdmType, size_t n, double badValue, float* d_out, hipStream_t stream);
 void launch_interpolation2data(const float* d_in, size_t n, int cdmType, double badValue, void* d_out, hipStream_t stream);
-
-bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
-                        hipStream_t stream);
 
 // f(T{}) with the C++ type of a numeric fimex_amd_datatype (char is signed on the reference's platforms); throws as cdm_type_size
 template <class F>

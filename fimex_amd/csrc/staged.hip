@@ -1,6 +1,6 @@
 // LDS-staged backward regrid (bilinear and bicubic) for gfx950: the bandwidth path of the headline metric.
 //
-// Same arithmetic as bilinear_apply / bicubic_apply in regrid.hip (src/interpolation.c:881-1028), different data
+// Same arithmetic as gather_apply in gather.hip (src/interpolation.c:881-1028), different data
 // movement.  A per-lane gather of the stencil straight from global memory asks the memory system for the same
 // 128-byte lines several times (measured on the 4000x3000 -> 2000x2000 rotated-pole case, profiles/LAB_NOTES_r01_r02.md, round 1: 3x the
 // ideal L2 requests and 1.6x the ideal fabric reads for the 2x2 stencil; the 4x4 stencil ran at 17 % of the HBM
@@ -669,7 +669,7 @@ void launch_staged_apply(const fimex_amd_regrid_plan& plan, const float* d_in, s
     launch_staged_t<float>(plan, a, nz, stream);
 }
 
-// The staged kernels on a variable's stored type (1- and 2-byte integers): what typed_apply (regrid.hip) does with
+// The staged kernels on a variable's stored type (1- and 2-byte integers): what gather_apply on a stored type (gather.hip) does with
 // gathers, through the LDS image.  false: not applicable (type, alignment), the caller takes another path.
 bool launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                hipStream_t stream)

@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(NT) staged_apply2(Staged2Args a)
     if (T.rsv[0] != 0) {
         // A tile whose footprint does not fit a slot even at the smallest width (an outlier among its positions: a grid
         // that wraps around the date line, isolated special points) reads its stencils straight from memory, like the
-        // gather kernels of regrid.hip; every other tile of the plan stays staged.
+        // gather kernels of gather.hip; every other tile of the plan stays staged.
         uint32_t p[PER];
 #pragma unroll
         for (int k = 0; k < PER; ++k) {

@@ -55,7 +55,7 @@ struct Staged2Args {
     const uint32_t* order;
     const uint32_t* chunkOff;
     const uint32_t *ldsA, *ldsB;
-    const uint32_t* pos;  // gather plan (regrid.hip): source cell of the stencil's corner, for the tiles that are not staged
+    const uint32_t* pos;  // gather plan (gather.hip): source cell of the stencil's corner, for the tiles that are not staged
     const float *xf, *yf;
     const double *xfd, *yfd;
     uint32_t outX, outY, tileH;

@@ -1,6 +1,6 @@
 // LDS-staged backward regrid, second form: the bandwidth path of the headline metric from round 2 on.
 //
-// Same arithmetic as staged.hip / regrid.hip (src/interpolation.c:862-1028) and the same idea -- a workgroup owns a tile of
+// Same arithmetic as staged.hip / gather.hip (src/interpolation.c:862-1028) and the same idea -- a workgroup owns a tile of
 // OUTPUT cells, streams the source row segments that tile needs HBM -> LDS by LDS-DMA for slice z + d while slice z is
 // interpolated out of LDS -- with the structure that the access calibration of round 2 asks for
 // (scripts/calib/stream_pattern.hip, profiles/calib/r02_stream_pattern_*.jsonl):

@@ -1,6 +1,6 @@
 // The reference's backward stencil rules, stated once: which source cells an output cell reads, how a plan entry says so,
 // and the arithmetic of mifi_get_values_f / _bilinear_f / _bicubic_f (src/interpolation.c:862-1028) operation by operation.
-// Every backward kernel (regrid.hip, staged.hip, staged2.hip) takes them from here, and so does the host shim of
+// Every backward kernel (backward_plan.hip, gather.hip, merge.hip, staged.hip, staged2.hip) takes them from here, and so does the host shim of
 // tests/test_stencil_math_host.py, which checks this file against the reference's arithmetic on the CPU, without a GPU:
 // everything is __host__ __device__ and free of device builtins.  Compiled with -ffp-contract=off: every multiply and add is a separate
 // IEEE operation in the reference's type and order.
@@ -9,6 +9,7 @@
 #include "plan.hpp"
 
 #include <cmath>
+#include <type_traits>
 
 #define FA_HD __host__ __device__ __forceinline__
 
@@ -159,6 +160,57 @@ FA_HD float bicubic_point(const float f[4][4], const double XM[4], const double 
         acc = (float)((double)acc + xmf * MY[i]);
     }
     return acc;
+}
+
+// ---- one plan entry, decoded: the step from (pos, fractions) to a value that every gather kernel (gather_entry.hpp), the merger and
+// the host shim take.  first: the stencil's first cell; dx / dy: the steps in cells to its next column / row, 0 for a neighbour
+// the entry lacks (bilinear border entries) and for an undefined entry, whose taps then all name one cell.
+template <int STENCIL>
+using frac_t = typename std::conditional<STENCIL == 4, double, float>::type;  // xf / yf, or xfd / yfd (nearest: none, pass 0)
+
+template <int STENCIL>
+struct EntryWeights {};
+template <>
+struct EntryWeights<2> {
+    float xf, yf;
+};
+template <>
+struct EntryWeights<4> {
+    double XM[4], MY[4];
+};
+
+template <int STENCIL>
+struct StencilEntry : EntryWeights<STENCIL> {
+    bool valid;
+    uint32_t first, dx, dy;
+
+    // taps[row][column]: the tap itself, bilinear_value (every form evaluated, one selected) or bicubic_point
+    FA_HD float combine(const float (&taps)[STENCIL][STENCIL]) const
+    {
+        if constexpr (STENCIL == 2) return bilinear_value(taps[0][0], taps[0][1], taps[1][0], taps[1][1], this->xf, this->yf);
+        else if constexpr (STENCIL == 4) return bicubic_point(taps, this->XM, this->MY);
+        else return taps[0][0];
+    }
+};
+
+template <int STENCIL>
+FA_HD StencilEntry<STENCIL> decode_entry(uint32_t pos, frac_t<STENCIL> xf, frac_t<STENCIL> yf, uint32_t ix)
+{
+    StencilEntry<STENCIL> e;
+    e.valid = pos != kInvalidPos;
+    e.first = pos;
+    e.dx = (e.valid && STENCIL != 1) ? 1u : 0u;
+    e.dy = (e.valid && STENCIL != 1) ? ix : 0u;
+    if constexpr (STENCIL == 2) {
+        e.xf = xf;
+        e.yf = yf;
+        if (is_nn(xf)) e.dx = 0u;
+        if (is_nn(yf)) e.dy = 0u;
+    } else if constexpr (STENCIL == 4) {
+        cubic_weights(xf, e.XM);
+        cubic_weights(yf, e.MY);
+    }
+    return e;
 }
 
 }  // namespace fimex_amd

@@ -1,5 +1,5 @@
 // Element conversions at the edges of a slice, shared by the conversion passes (convert.hip) and the regrid kernels that
-// read and write a variable's stored type directly (regrid.hip): data2InterpolationArray / interpolationArray2Data,
+// read and write a variable's stored type directly (gather_entry.hpp): data2InterpolationArray / interpolationArray2Data,
 // src/CDMInterpolator.cc:115-124.
 #pragma once
 

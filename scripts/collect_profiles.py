@@ -29,7 +29,8 @@ def run(cmd):
 def timed_dispatches(rows, name_key):
     """rows of a per-dispatch CSV in dispatch order -> the STEPS launches of the staged apply kernel before the first gather launch."""
     rows = sorted(rows, key=lambda x: int(x.get("Dispatch_Id") or x.get("Dispatch_ID") or 0))
-    is_gather = lambda n: ("bilinear_apply" in n or "nearest_apply" in n or "bicubic_apply" in n) and "staged" not in n
+    # gather_apply; traces from before it: bilinear_apply / nearest_apply / bicubic_apply
+    is_gather = lambda n: any(k in n for k in ("gather_apply", "bilinear_apply", "nearest_apply", "bicubic_apply")) and "staged" not in n
     first_gather = next((i for i, x in enumerate(rows) if is_gather(x[name_key])), len(rows))
     staged = [x for x in rows[:first_gather] if "staged_apply" in x[name_key]]
     return staged[-STEPS:]

@@ -1,4 +1,4 @@
-"""Driver of the scripts that compare two builds of the library on the GPU (compare_staged2_builds.py, compare_projection_builds.py).
+"""Driver of the scripts that compare two builds of the library on the GPU (compare_staged2_builds.py, compare_projection_builds.py, compare_forward_builds.py, compare_gather_builds.py).
 
 The comparing script is its own worker: `script --worker [--lib DIR]` loads this tree's library, or the one in DIR, runs every case
 once and prints one JSON line per case: {"case": name, "sha256": of the output bytes} and, for a timed case, "seconds": the timed

@@ -1,6 +1,6 @@
 // Host shim of fimex_amd/csrc/stencil_math.hpp for tests/test_stencil_math_host.py: the header the backward kernels compile,
-// evaluated on the CPU the way the kernels use it -- classify, encode the plan entry, decode it, gather the stencil,
-// combine.  Built for the host only by fimex_amd/build.py (hipcc --cuda-host-only -ffp-contract=off); needs no GPU.
+// evaluated on the CPU the way the kernels use it -- classify, encode the plan entry, decode it (decode_entry, the decoder the
+// gather kernels compile), gather the stencil, combine.  Built for the host only by fimex_amd/build.py (hipcc --cuda-host-only -ffp-contract=off); needs no GPU.
 #include "stencil_math.hpp"
 
 using namespace fimex_amd;
@@ -24,30 +24,20 @@ void eval(const float* field, int64_t ix, int64_t iy, int64_t nz, const double* 
         const uint32_t pos = encode_pos(c, ix);
         const float xf = STENCIL == 2 ? encode_frac_bilinear(c, c.xa == c.xb, px[p]) : 0.f;
         const float yf = STENCIL == 2 ? encode_frac_bilinear(c, c.ya == c.yb, py[p]) : 0.f;
-        double XM[4], MY[4];
-        cubic_weights(encode_frac_bicubic(c, px[p]), XM);
-        cubic_weights(encode_frac_bicubic(c, py[p]), MY);
-        // ... and as the apply kernels and the tile scans read it
-        const CellNeed e = entry_need<STENCIL>(pos, xf, yf, ix);
-        if (!same_need(c, e)) cls[p] = kEntryDisagrees;
+        // ... and as the tile scans and the gather kernels read it (the decoder of gather_entry.hpp, cell steps instead of byte steps)
+        const CellNeed need = entry_need<STENCIL>(pos, xf, yf, ix);
+        using frac = frac_t<STENCIL>;
+        const StencilEntry<STENCIL> e = decode_entry<STENCIL>(pos, STENCIL == 4 ? (frac)encode_frac_bicubic(c, px[p]) : (frac)xf,
+                                                              STENCIL == 4 ? (frac)encode_frac_bicubic(c, py[p]) : (frac)yf, (uint32_t)ix);
+        if (!same_need(c, need)) cls[p] = kEntryDisagrees;
         else if (pos == kInvalidPos) cls[p] = kUndefined;
         else cls[p] = STENCIL == 2 ? (is_nn(xf) ? (is_nn(yf) ? kNearestBoth : kLinearY) : (is_nn(yf) ? kLinearX : kInterior)) : kInterior;
         for (int64_t z = 0; z < nz; ++z) {
             const float* s = field + z * ix * iy;
-            float r = undefined_f();
-            if (pos == kInvalidPos) {
-            } else if (STENCIL == 1) {
-                r = s[pos];
-            } else if (STENCIL == 2) {  // a missing neighbour repeats the cell itself, as in the kernels
-                const int64_t dx = is_nn(xf) ? 0 : 1, dy = is_nn(yf) ? 0 : ix;
-                r = bilinear_value(s[pos], s[pos + dx], s[pos + dy], s[pos + dx + dy], xf, yf);
-            } else {
-                float f[4][4];
-                for (int i = 0; i < 4; ++i)
-                    for (int j = 0; j < 4; ++j) f[i][j] = s[pos + i * ix + j];
-                r = bicubic_point(f, XM, MY);
-            }
-            out[p * nz + z] = r;
+            float taps[STENCIL][STENCIL];
+            for (int i = 0; i < STENCIL; ++i)
+                for (int j = 0; j < STENCIL; ++j) taps[i][j] = e.valid ? s[e.first + i * e.dy + j * e.dx] : 0.f;  // undefined: loads dropped
+            out[p * nz + z] = e.valid ? e.combine(taps) : undefined_f();
         }
     }
 }

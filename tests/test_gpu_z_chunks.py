@@ -10,11 +10,13 @@ smallest shapes at which the launch rule itself chooses zPerBlock > 1.  The prod
 the zPerBlock it gives: a retuned launcher must fail them, not turn them back into one-slice tests.
 
 Passes of the main loop per chunk (tail slices behind them), by (zPerBlock, nz):
-  nearest_apply<16>            (16, 16) 1; (17, 35) 1 + 1; (40, 83) 2 + 8; product (17, 17) 1 + 1
-  bilinear_apply<8>            (16, 16) 2; (17, 35) 2 + 1; (8, 20) 1; (40, 83) 5; product (17, 17) 2 + 1
-  bilinear_apply<16 / 4 / 2>   (17, 35) 1 + 1 / 4 + 1 / 8 + 1
-  bicubic_apply<2>             (16, 16) 8; (17, 35) 8 + 1; (8, 20) 4; (3, 7) 1 + 1; (40, 83) 20
-  typed_apply, ZC = 8          (8, 19) 1, last chunk 3 tail slices; (17, 19) 2 + 1
+  gather_apply<STENCIL, ZC, T> (csrc/gather.hip):
+  <1, 16, float>               (16, 16) 1; (17, 35) 1 + 1; (40, 83) 2 + 8; product (17, 17) 1 + 1
+  <2, 8, float>                (16, 16) 2; (17, 35) 2 + 1; (8, 20) 1; (40, 83) 5; product (17, 17) 2 + 1
+  <2, 16 / 4 / 2, float>       (17, 35) 1 + 1 / 4 + 1 / 8 + 1
+  <4, 2, float>                (16, 16) 8; (17, 35) 8 + 1; (8, 20) 4; (3, 7) 1 + 1; (40, 83) 20
+  <1 | 2, 8, stored types>     (8, 19) 1, last chunk 3 tail slices; (17, 19) 2 + 1
+  apply_few<1 | 2, 2 / 4 / 8>  one slice, FEW_CELLS cells per lane
   rotate_values_vec4           VECTOR_ZPB 2 / 3 / 4 / 5 / 9: 1 / 1 + 1 / 2 / 2 + 1 / 4 + 1; product (3, 80) 1 + 1
   rotate_direction_vec4        the same
   rotate_direction             VECTOR_ZPB 4 / 5 / 9: 1 / 1 + 1 / 2 + 1; product (5, 80) 1 + 1
@@ -66,7 +68,7 @@ def _check_plan_info(plan, method):
     info = plan.info()
     assert info["undefinedCells"] > 0  # write_undefined over a multi-slice chunk
     if method == oracle.BILINEAR:
-        assert info["borderCells"] > 0  # the per-slice border branch inside a multi-slice chunk
+        assert info["borderCells"] > 0  # border entries (zero steps for the neighbours they lack) inside a multi-slice chunk
 
 
 # ------------------------------------------------------------------------------------------- 1. gather kernels on floats, forced ZPB
@@ -99,7 +101,7 @@ def _gather_on_device(fa, method, px, py, f, geometry):
 @pytest.mark.parametrize("method", METHODS, ids=METHOD_IDS)
 @pytest.mark.parametrize("zpb,nz", ZPB_NZ)
 def test_gather_main_loops_with_forced_chunks(fa, monkeypatch, method, zpb, nz, tuning_build):
-    """nearest_apply<16>, bilinear_apply<8> and bicubic_apply<2> with chunks of several slices: a chunk of 17 is 16 + 1, 2 x 8 + 1 and
+    """gather_apply<1, 16>, <2, 8> and <4, 2> on floats with chunks of several slices: a chunk of 17 is 16 + 1, 2 x 8 + 1 and
     8 x 2 + 1 slices; where ZPB does not divide nz the last chunk is shorter than the others"""
     monkeypatch.setenv("FIMEX_AMD_ZPB", str(zpb))
     px, py, f, want = _gather_case(method, nz)
@@ -111,12 +113,24 @@ def test_gather_main_loops_with_forced_chunks(fa, monkeypatch, method, zpb, nz, 
                                    {"BILINEAR_ZC": "16", "NT": "0"}, {"BILINEAR_ZC": "4", "NT": "0"}],
                          ids=lambda k: "-".join("%s%s" % kv for kv in sorted(k.items())))
 def test_bilinear_gather_other_instantiations(fa, monkeypatch, knobs, tuning_build):
-    """the other bilinear_apply<ZC, NT> kernels that the sweeps launch, on chunks of 17 slices and a last chunk of one"""
+    """the other gather_apply<2, ZC, float, NT> kernels that the sweeps launch, on chunks of 17 slices and a last chunk of one"""
     monkeypatch.setenv("FIMEX_AMD_ZPB", "17")
     for k, v in knobs.items():
         monkeypatch.setenv("FIMEX_AMD_" + k, v)
     px, py, f, want = _gather_case(oracle.BILINEAR, 35)
     got = _gather_on_device(fa, oracle.BILINEAR, px, py, f, GATHER_GEOMETRY)
+    assert cases.same(got, want), cases.describe_mismatch(got, want)
+
+
+@pytest.mark.parametrize("method", [oracle.NEAREST, oracle.BILINEAR], ids=["nearest", "bilinear"])
+@pytest.mark.parametrize("cells", [2, 4, 8])
+def test_one_slice_kernels_with_every_cells_per_lane(fa, monkeypatch, method, cells, tuning_build):
+    """apply_few<1 | 2, CELLS> on one slice: 64 x (4 * CELLS) tiles on a 100 x 70 target, so every shape has lanes beyond the slice and
+    partly filled tiles (100 % 64 != 0; 70 is no multiple of 8, 16 or 32); undefined entries (their loads are dropped) and bilinear
+    border entries lie among the cells of one lane"""
+    monkeypatch.setenv("FIMEX_AMD_FEW_CELLS", str(cells))
+    px, py, f, want = _gather_case(method, 1)
+    got = _gather_on_device(fa, method, px, py, f, GATHER_GEOMETRY)  # asserts the plan's undefined and border cells
     assert cases.same(got, want), cases.describe_mismatch(got, want)
 
 
@@ -145,8 +159,8 @@ def _typed_case(method, dt, bad):
 @pytest.mark.parametrize("dt,bad", TYPED, ids=lambda p: p.__name__ if isinstance(p, type) else "bad%g" % p)
 @pytest.mark.parametrize("zpb", [8, 17])
 def test_typed_gather_main_loops_with_forced_chunks(fa, monkeypatch, method, dt, bad, zpb, tuning_build):
-    """typed_apply on the stored type with 8 slices behind one descriptor: chunks of 8, 8 and 3 slices, and of 2 x 8 + 1 and 2; the
-    bilinear main loop evaluates bilinear_forms(...).inter, the tail bilinear_value; against the oracle's three steps"""
+    """gather_apply on the stored type with 8 slices behind one descriptor: chunks of 8, 8 and 3 slices, and of 2 x 8 + 1 and 2
+    (bicubic: one slice at a time); against the oracle's three steps"""
     import torch
     monkeypatch.setenv("FIMEX_AMD_TYPED_STAGED", "0")
     monkeypatch.setenv("FIMEX_AMD_TYPED_FUSED", "2")
@@ -167,7 +181,7 @@ def test_typed_gather_main_loops_with_forced_chunks(fa, monkeypatch, method, dt,
 
 # -------------------------------------------------------------------------------------------- 3. gather kernels, the launch rule itself
 def _gather_z_per_block(outX, outY, nz):
-    """make_args of csrc/regrid.hip (:337-358) at its defaults: 64 x 4 tiles, chunks so that 256 * 8 * 4 workgroups exist, at most 40
+    """make_args of csrc/gather.hip at its defaults: 64 x 4 tiles, chunks so that 256 * 8 * 4 workgroups exist, at most 40
     slices per workgroup"""
     tiles = _ceil_div(outX, 64) * _ceil_div(outY, 4)
     chunks = max(1, min(nz, _ceil_div(256 * 8 * 4, tiles)))
@@ -189,7 +203,7 @@ def _product_inputs():
 @pytest.mark.parametrize("method", [oracle.NEAREST, oracle.BILINEAR], ids=["nearest", "bilinear"])
 def test_gather_main_loops_under_the_launch_rule(fa, method):
     """the product library at the smallest shape at which its own rule gives zPerBlock > 1: 17 slices in one workgroup, 16 + 1 for
-    nearest_apply<16> and 2 x 8 + 1 for bilinear_apply<8>"""
+    gather_apply<1, 16, float> and 2 x 8 + 1 for gather_apply<2, 8, float>"""
     import torch
     inX, inY, outX, outY = PRODUCT_GEOMETRY
     assert _gather_z_per_block(outX, outY, PRODUCT_NZ) == 17

@@ -45,7 +45,7 @@ def test_timed_launches_are_the_ones_before_the_verification():
     extras), the timed ones are the STEPS launches that directly precede the first gather-kernel launch."""
     cp = _script("collect_profiles")
     staged = "void fimex_amd::(anonymous namespace)::staged_apply2<2, 1024, 4, 5, false, 2>(fimex_amd::(anonymous namespace)::Staged2Args)"
-    gather = "void fimex_amd::(anonymous namespace)::bilinear_apply<8, true>(fimex_amd::(anonymous namespace)::ApplyArgs, unsigned int const*, float const*, float const*)"
+    gather = "void fimex_amd::(anonymous namespace)::gather_apply<2, 8, float, true>(fimex_amd::(anonymous namespace)::ApplyArgs, fimex_amd::Element<float>::Params, unsigned int const*, float const*, float const*)"
     rows, d = [], 1
     for k in range(61):  # probing + tuning + warm-up
         rows.append({"Dispatch_Id": str(d), "Kernel_Name": staged, "tag": "before"}); d += 1
