@@ -19,6 +19,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "staged_layout.hpp"
 
 #include <functional>
 #include <mutex>
@@ -36,6 +37,8 @@ enum class Aggregate : int { Sum = 0, Mean = 1, Median = 2, Max = 3, Min = 4 };
 }  // namespace fimex_amd
 
 namespace fimex_amd {
+static_assert(layout::kXcds == (uint32_t)kXcds, "staged_layout.hpp deals workgroups to the XCDs of common.hpp");
+
 // LDS-staged form of a bilinear / bicubic plan (staged.hip): per tile the source row segments to stream into
 // LDS, per output cell the 16-bit LDS offsets of its stencil rows; the fractions are those of the gather plan.
 struct StagedPlan {
@@ -49,13 +52,7 @@ struct StagedPlan {
 
 // Second LDS-staged form (staged2_plan.hip builds it, staged2.hip and staged2_typed.hip run it): tiles of one height and varying width (narrower where the source footprint of an
 // output cell is larger, so that every tile fits the same LDS budget), workgroups of 256-1024 threads, and per tile the
-// list of 16-byte source chunks itself instead of row segments.
-struct StagedTile {
-    uint32_t x0, y0, w;     // output columns [x0, x0 + w) of rows [y0, y0 + tileH)
-    uint32_t nChunks;       // 16-byte chunks streamed per slice
-    uint32_t chunkBase;     // first entry in chunkOff
-    uint32_t rsv[3];
-};
+// list of 16-byte source chunks itself instead of row segments.  StagedTile and the rules that cut the tiles: staged_layout.hpp.
 struct Staged2Plan {
     bool valid = false;
     uint32_t nt = 0, per = 0, kmax = 0, tileH = 0, tileWMax = 0, nTiles = 0, gridX = 0, ldsBytes = 0, depth = 2;

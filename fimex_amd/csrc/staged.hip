@@ -47,96 +47,46 @@ __global__ void __launch_bounds__(kBlock) build_tiles(const double* __restrict__
                                                       uint2* __restrict__ tileHdr, uint32_t* __restrict__ ldsA,
                                                       uint32_t* __restrict__ ldsB, BuildCounters* counters)
 {
-    __shared__ int shRmin, shRmax;
-    __shared__ int rowMin[kMaxRows], rowMax[kMaxRows];
-    __shared__ uint32_t rowChunk[kMaxRows + 1];
-    __shared__ int shOverflow;
+    __shared__ TileFootprint fp;
     const uint32_t tile = blockIdx.x;
     const uint32_t tx = tile % g.tilesX, ty = tile / g.tilesX;
     const uint32_t perLane = (g.tileW * g.tileH) / kBlock;
-    if (threadIdx.x == 0) { shRmin = 0x7FFFFFFF; shRmax = -1; shOverflow = 0; }
-    __syncthreads();
     // lane owns column lx of rows ly0, ly0 + rowsPerPass, ... of the tile (a wave covers 64 consecutive x)
     const uint32_t lx = threadIdx.x % g.tileW;
     const uint32_t rowsPerPass = kBlock / g.tileW;
     const uint32_t ly0 = threadIdx.x / g.tileW;
-    for (uint32_t k = 0; k < perLane; ++k) {
-        const uint32_t x = tx * g.tileW + lx, y = ty * g.tileH + ly0 + k * rowsPerPass;
-        if (x < g.outX && y < g.outY) {
-            const size_t cell = (size_t)y * g.outX + x;
-            const CellNeed c = classify<STENCIL>(px[cell], py[cell], ix, iy);
-            if (c.valid) { atomicMin(&shRmin, (int)c.ya); atomicMax(&shRmax, (int)c.yb); }
-        }
-    }
-    __syncthreads();
-    const int rmin = shRmin;
-    const int nr = (shRmax >= rmin) ? shRmax - rmin + 1 : 0;
-    if (nr > kMaxRows) {
-        if (threadIdx.x == 0) { atomicAdd(&counters->overflow, 1ull); tileHdr[tile] = make_uint2(0, 0); }
-        return;
-    }
-    for (int i = threadIdx.x; i < nr; i += kBlock) { rowMin[i] = 0x7FFFFFFF; rowMax[i] = -1; }
-    __syncthreads();
-    for (uint32_t k = 0; k < perLane; ++k) {
-        const uint32_t x = tx * g.tileW + lx, y = ty * g.tileH + ly0 + k * rowsPerPass;
-        if (x < g.outX && y < g.outY) {
-            const size_t cell = (size_t)y * g.outX + x;
-            const CellNeed c = classify<STENCIL>(px[cell], py[cell], ix, iy);
-            if (c.valid)
-                for (int64_t r = c.ya; r <= c.yb; ++r) {
-                    atomicMin(&rowMin[r - rmin], (int)c.xa);
-                    atomicMax(&rowMax[r - rmin], (int)c.xb);
-                }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t acc = 0;
-        for (int i = 0; i < nr; ++i) {
-            rowChunk[i] = acc;
-            if (rowMax[i] >= 0) {
-                const int xs = rowMin[i] & ~3;  // 16-byte aligned start (ix % 4 == 0)
-                rowMin[i] = xs;
-                acc += (uint32_t)((rowMax[i] - xs) / 4 + 1);
+    auto cells = [&](auto&& f) {
+        for (uint32_t k = 0; k < perLane; ++k) {
+            const uint32_t x = tx * g.tileW + lx, y = ty * g.tileH + ly0 + k * rowsPerPass;
+            if (x < g.outX && y < g.outY) {
+                const size_t cell = (size_t)y * g.outX + x;
+                f(cell, classify<STENCIL>(px[cell], py[cell], ix, iy));
             }
         }
-        rowChunk[nr] = acc;
-        if (acc > g.capChunks) shOverflow = 1;
-    }
-    __syncthreads();
-    if (shOverflow) {
+    };
+    // Chunks of 4 cells.  This form takes only sources with ix % 4 == 0 (build_staged_plan): a segment that starts on a 16-byte
+    // boundary of the slice then starts on one of its row (the column & ~3), and none reaches past the end of the slice, so what
+    // segments() does for other row lengths and chunk sizes never applies here.
+    const int nr = fp.scan(cells);
+    if (nr < 0 || !fp.segments(nr, ix, iy, 4, g.capChunks)) {
         if (threadIdx.x == 0) { atomicAdd(&counters->overflow, 1ull); tileHdr[tile] = make_uint2(0, 0); }
         return;
     }
     uint32_t* rows = tileRows + (size_t)tile * 2 * kMaxRows;
     for (int i = threadIdx.x; i < nr; i += kBlock) {
-        rows[2 * i] = (rowMax[i] >= 0) ? (uint32_t)((int64_t)(rmin + i) * ix + rowMin[i]) : 0u;
-        rows[2 * i + 1] = rowChunk[i];
+        rows[2 * i] = fp.has_row(i) ? (uint32_t)fp.segment_start(i, ix) : 0u;
+        rows[2 * i + 1] = fp.rowChunk[i];
     }
     if (threadIdx.x == 0) {
-        tileHdr[tile] = make_uint2((uint32_t)nr, rowChunk[nr]);
-        atomicAdd(&counters->stagedChunks, (unsigned long long)rowChunk[nr]);
+        tileHdr[tile] = make_uint2((uint32_t)nr, fp.rowChunk[nr]);
+        atomicAdd(&counters->stagedChunks, (unsigned long long)fp.rowChunk[nr]);
     }
-    for (uint32_t k = 0; k < perLane; ++k) {
-        const uint32_t x = tx * g.tileW + lx, y = ty * g.tileH + ly0 + k * rowsPerPass;
-        if (x < g.outX && y < g.outY) {
-            const size_t cell = (size_t)y * g.outX + x;
-            const CellNeed c = classify<STENCIL>(px[cell], py[cell], ix, iy);
-            uint32_t a = kInvalidPos, b = kInvalidPos;
-            if (c.valid) {
-                uint32_t off[4];
-                for (int r = 0; r < 4; ++r) {
-                    const int64_t row = (c.ya + r <= c.yb) ? c.ya + r : c.yb;  // missing rows repeat the last one
-                    const int i = (int)(row - rmin);
-                    off[r] = rowChunk[i] * 4 + (uint32_t)(c.xa - rowMin[i]);
-                }
-                a = off[0] | (off[1] << 16);
-                b = off[2] | (off[3] << 16);
-            }
-            ldsA[cell] = a;
-            if (STENCIL == 4) ldsB[cell] = b;
-        }
-    }
+    cells([&](size_t cell, const CellNeed& c) {
+        uint32_t a, b;
+        fp.offsets(c, 4, a, b);
+        ldsA[cell] = a;
+        if (STENCIL == 4) ldsB[cell] = b;
+    });
 }
 
 struct StagedArgs {
@@ -235,24 +185,11 @@ __global__ void __launch_bounds__(kBlock) staged_apply(StagedArgs a)
     uint32_t* shRows = reinterpret_cast<uint32_t*>(smem + NBUF * kBufFloats);  // [2 * nr]
     uint32_t* shPiece = shRows + 2 * kMaxRows;                                   // kWide: first piece of every segment, [nr + 1]
 
-    // workgroup -> tile.  Workgroups are dealt round-robin over the 8 XCDs (b % 8 shares an L2):
-    //   xcdRemap 0: tiles in dispatch order (neighbours on different XCDs) -- the default, measured as good as any;
-    //   xcdRemap 1: each XCD owns one contiguous band of tile rows;
-    //   xcdRemap >= 2: tile rows dealt to the XCDs in stripes of (xcdRemap - 1) rows.
+    // workgroup -> tile (first_form_tile, staged_layout.hpp).  Workgroups are dealt round-robin over the 8 XCDs (b % 8 shares an
+    // L2); xcdRemap 0, tiles in dispatch order, is the default and measured as good as any.
     uint32_t b = blockIdx.x, zc = blockIdx.y;
-    if (a.nZChunks != 0) {  // workgroup s runs on XCD s % 8; the k-th workgroup of an XCD is z chunk k % n of the XCD's tile k / n
-        const uint32_t k = blockIdx.x / kXcds;
-        zc = k % a.nZChunks;
-        b = (k / a.nZChunks) * kXcds + blockIdx.x % kXcds;
-    }
-    uint32_t tile = b;
-    if (a.xcdRemap == 1) {
-        tile = (b % kXcds) * a.tilesPerXcd + b / kXcds;
-    } else if (a.xcdRemap >= 2) {
-        const uint32_t stripe = (a.xcdRemap - 1) * a.g.tilesX;
-        const uint32_t idx = b / kXcds;
-        tile = ((idx / stripe) * kXcds + b % kXcds) * stripe + idx % stripe;
-    }
+    if (a.nZChunks != 0) flat_workgroup(blockIdx.x, a.nZChunks, b, zc);  // flat grid in tile-major order
+    const uint32_t tile = first_form_tile(b, a.xcdRemap, a.tilesPerXcd, a.g.tilesX);
     if (tile >= a.g.nTiles) return;
     const uint32_t z0 = zc * a.zPerBlock;
     const uint32_t z1 = min(a.nz, z0 + a.zPerBlock);
@@ -609,10 +546,8 @@ void launch_staged_t(const fimex_amd_regrid_plan& plan, StagedArgs& a, size_t nz
     // STAGE_ORDER 1: tile-major launch order as in staged2.hip (the z chunks of a tile start together on one XCD, tile rows dealt
     // to the XCDs one by one); 0: all tiles of z chunk 0, then chunk 1, ...
     const bool tileMajor = tuning("STAGE_ORDER", 0) == 1;
-    uint32_t zpb = (uint32_t)tuning("STAGE_ZPB", tileMajor ? 25 : 50);
-    if (zpb < 1) zpb = 1;
-    if (zpb > nz) zpb = (uint32_t)nz;
-    a.zPerBlock = zpb;
+    const FirstFormZ z = first_form_z(nz, (uint32_t)tuning("STAGE_ZPB", tileMajor ? 25 : 50));
+    a.zPerBlock = z.zPerBlock;
     // tile -> XCD map: stored types (1 and 2 bytes) with the 1 x 1 and 2 x 2 stencils run 3.5-4.3 % faster with tile rows dealt to the
     // XCDs one by one (packed shorts, 200 slices: bilinear 1.71 -> 1.65 ms, nearest 1.56 -> 1.49 ms in three processes,
     // profiles/r02_typed_order*.jsonl); floats and the 4 x 4 stencil keep the dispatch order
@@ -621,13 +556,9 @@ void launch_staged_t(const fimex_amd_regrid_plan& plan, StagedArgs& a, size_t nz
     a.ablate = (uint32_t)tuning("ABLATE", 0);
     a.storeAux = (uint32_t)tuning("STORE_AUX", 2);
     a.loadAux = (uint32_t)tuning("LOAD_AUX", 0);
-    a.tilesPerXcd = (uint32_t)ceil_div(s.nTiles, kXcds);
-    uint32_t gridX = a.tilesPerXcd * kXcds;
-    if (a.xcdRemap >= 2) {  // whole stripes per XCD
-        const uint32_t stripe = (a.xcdRemap - 1) * s.tilesX;
-        gridX = (uint32_t)ceil_div(s.nTiles, (size_t)stripe * kXcds) * stripe * kXcds;
-    }
-    const size_t chunks = ceil_div(nz, (size_t)zpb);
+    a.tilesPerXcd = first_form_tiles_per_xcd(s.nTiles);
+    const uint32_t gridX = first_form_grid(s.nTiles, s.tilesX, a.xcdRemap);
+    const size_t chunks = z.chunks;
     FA_REQUIRE(chunks <= 65535 && (size_t)gridX * chunks <= 0x7FFFFFFFu, "too many z chunks for one launch");
     a.nZChunks = tileMajor ? (uint32_t)chunks : 0u;
     const dim3 grid(tileMajor ? gridX * (uint32_t)chunks : gridX, tileMajor ? 1u : (uint32_t)chunks, 1);

@@ -8,14 +8,6 @@
 
 namespace fimex_amd {
 
-constexpr uint32_t kSpareBytes = 1024;  // one wave instruction of LDS-DMA behind the ring (see SliceRing, staged2_ring.hpp)
-
-// chunks of one slot: the workgroup's LDS less the spare KiB, in `depth` equal slots of whole wave instructions
-inline uint32_t slot_chunks(uint32_t ldsBytes, uint32_t depth)
-{
-    return ((ldsBytes - kSpareBytes) / depth / 16u) & ~63u;
-}
-
 struct Shape2 {
     int nt, per, kmax;
     uint32_t depth;         // slices of the ring: one or two in flight while one is interpolated
@@ -45,8 +37,6 @@ bool build_staged2_form(const fimex_amd_regrid_plan& plan, Staged2Plan& form, co
                         uint32_t stripe, uint32_t cpc, hipStream_t stream);
 
 namespace {
-
-constexpr int kMaxZChunks = 31;
 
 struct Staged2Args {
     const float* in;
@@ -97,15 +87,11 @@ inline Staged2Args staged2_args(const fimex_amd_regrid_plan& plan, const Staged2
     return a;
 }
 
-// n z chunks of one size (the first nz % n of them one slice longer), as consecutive workgroups of a tile
-inline void even_z_split(Staged2Args& a, size_t nz, uint32_t n)
+// the z chunks of a launch into the kernels' argument; flat: the grid is one-dimensional (flat_workgroup, staged_layout.hpp)
+inline void set_z_chunks(Staged2Args& a, const ZChunks& zc, bool flat)
 {
-    for (uint32_t c = 0, z = 0; c < n; ++c) {
-        a.zStart[c] = z;
-        z += (uint32_t)nz / n + (c < (uint32_t)nz % n ? 1u : 0u);
-    }
-    a.zStart[n] = (uint32_t)nz;
-    a.nZChunks = n;
+    std::copy(zc.zStart, zc.zStart + kMaxZChunks + 1, a.zStart);
+    a.nZChunks = flat ? zc.n : 0u;
 }
 
 // the workgroup shape a float launch runs: the plan's choice (fimex_amd_regrid_plan_tune_device), or STAGE2_USE_ALT 0 / 1 in the
@@ -124,28 +110,16 @@ inline const Staged2Plan& staged2_shape_of(const fimex_amd_regrid_plan& plan)
 // chunks of one size (about STAGE2_ZPB slices).  Measured on the benchmark plan (round 2's sweeps, profiles/LAB_NOTES_r01_r02.md): bilinear
 // 2.40 -> 2.32 ms, nearest 2.32 -> 2.21 ms, 25 slices 0.322 -> 0.303 ms.
 // Chunk-major order (STAGE2_ORDER 0, round 1 and early round 2): all tiles of chunk 0, then chunk 1, ...; the chunks shrink
-// towards the end of the launch so that the last workgroups are short ones (STAGE2_ZTAIL).
+// towards the end of the launch so that the last workgroups are short ones (STAGE2_ZTAIL).  The rules: float_z_chunks.
 inline dim3 staged2_z_chunks(Staged2Args& a, const Staged2Plan& s, size_t nz)
 {
     const bool tileMajor = tuning("STAGE2_ORDER", 1) == 1;
-    uint32_t zpb = (uint32_t)tuning("STAGE2_ZPB", tileMajor ? 25 : 50);
+    const uint32_t zpb = (uint32_t)tuning("STAGE2_ZPB", tileMajor ? 25 : 50);
     const uint32_t ztail = tileMajor ? 0u : (uint32_t)tuning("STAGE2_ZTAIL", 10);  // 0: chunks of one size
-    if (zpb < 1) zpb = 1;
-    const size_t mostChunks = tileMajor ? 16 : (size_t)kMaxZChunks - 6;
-    if (ceil_div(nz, (size_t)zpb) > mostChunks) zpb = (uint32_t)ceil_div(nz, mostChunks);
-    uint32_t nChunks = tileMajor ? (uint32_t)ceil_div(nz, (size_t)zpb) : 0u;
-    if (tileMajor) even_z_split(a, nz, nChunks);
-    for (uint32_t z = 0; !tileMajor && z < nz;) {
-        const uint32_t rem = (uint32_t)nz - z;
-        uint32_t size = zpb;
-        if (ztail > 0 && rem <= 2 * zpb) size = std::max(ztail, (rem + 1) / 2);
-        if (size > rem || rem - size < (ztail + 1) / 2) size = rem;
-        FA_REQUIRE(nChunks < (uint32_t)kMaxZChunks, "too many z chunks for one launch");
-        a.zStart[nChunks++] = z;
-        z += size;
-    }
-    a.zStart[nChunks] = (uint32_t)nz;
-    return dim3(tileMajor ? s.gridX * nChunks : s.gridX, tileMajor ? 1u : nChunks, 1);
+    ZChunks zc;
+    FA_REQUIRE(float_z_chunks(nz, tileMajor, zpb, ztail, zc), "too many z chunks for one launch");
+    set_z_chunks(a, zc, tileMajor);
+    return dim3(tileMajor ? s.gridX * zc.n : s.gridX, tileMajor ? 1u : zc.n, 1);
 }
 
 }  // namespace

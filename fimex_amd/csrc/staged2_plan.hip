@@ -23,8 +23,6 @@ namespace fimex_amd {
 
 namespace {
 
-// One workgroup per tile.  emit == 0: counts the 16-byte chunks of the tile's row segments (tiles[t].nChunks, ~0u = does not
-// fit).  emit == 1: writes the chunk list and every output cell's LDS offsets (16 bits per stencil row, in floats).
 // Where the stencil of an output cell lies (see build_staged2_form, staged2.hpp): px / py, or pos / xf / yf (entry_need, stencil_math.hpp).
 struct NeedSource {
     const double* px = nullptr;
@@ -41,6 +39,9 @@ __device__ __forceinline__ CellNeed need_of(const NeedSource& n, size_t cell, in
     return entry_need<STENCIL>(n.pos[cell], STENCIL == 2 ? n.xf[cell] : 0.f, STENCIL == 2 ? n.yf[cell] : 0.f, ix);
 }
 
+// One workgroup per tile, on the tile's footprint (TileFootprint, staged_common.hpp).  emit == 0: counts the 16-byte chunks of the
+// tile's row segments (tiles[t].nChunks, kTileTooLarge = does not fit).  emit == 1: writes the chunk list and every output cell's
+// LDS offsets (16 bits per stencil row, in elements).
 // cpc: source cells per 16-byte chunk (4 for float slices, 8 / 16 for slices of 2- / 1-byte elements); LDS offsets count elements.
 template <int STENCIL>
 __global__ void __launch_bounds__(kBlock) tile_scan(NeedSource need, int64_t ix, int64_t iy,
@@ -48,98 +49,41 @@ __global__ void __launch_bounds__(kBlock) tile_scan(NeedSource need, int64_t ix,
                                                     uint32_t capChunks, int emit, uint32_t* __restrict__ chunkOff,
                                                     uint32_t* __restrict__ ldsA, uint32_t* __restrict__ ldsB, uint32_t cpc)
 {
-    __shared__ int shRmin, shRmax, shFail;
-    __shared__ int rowMin[kMaxRows], rowMax[kMaxRows];
-    __shared__ uint32_t rowChunk[kMaxRows + 1];
+    __shared__ TileFootprint fp;
     const uint32_t t = blockIdx.x;
     const StagedTile T = tiles[t];
-    if (T.rsv[0] != 0) return;  // not staged (see build_shape)
+    if (T.rsv[0] != 0) return;  // not staged (see refine_bands, staged_layout.hpp)
     const uint32_t nCells = T.w * tileH;
-    if (threadIdx.x == 0) { shRmin = 0x7FFFFFFF; shRmax = -1; shFail = 0; }
-    __syncthreads();
-    for (uint32_t e = threadIdx.x; e < nCells; e += kBlock) {
-        const uint32_t y = T.y0 + e / T.w, x = T.x0 + e % T.w;
-        if (y >= outY) continue;
-        const size_t cell = (size_t)y * outX + x;
-        const CellNeed c = need_of<STENCIL>(need, cell, ix, iy);
-        if (c.valid) { atomicMin(&shRmin, (int)c.ya); atomicMax(&shRmax, (int)c.yb); }
-    }
-    __syncthreads();
-    const int rmin = shRmin;
-    const int nr = (shRmax >= rmin) ? shRmax - rmin + 1 : 0;
-    if (nr > kMaxRows) {
-        if (threadIdx.x == 0 && !emit) tiles[t].nChunks = 0xFFFFFFFFu;
-        return;
-    }
-    for (int i = threadIdx.x; i < nr; i += kBlock) { rowMin[i] = 0x7FFFFFFF; rowMax[i] = -0x7FFFFFFF; }
-    __syncthreads();
-    for (uint32_t e = threadIdx.x; e < nCells; e += kBlock) {
-        const uint32_t y = T.y0 + e / T.w, x = T.x0 + e % T.w;
-        if (y >= outY) continue;
-        const size_t cell = (size_t)y * outX + x;
-        const CellNeed c = need_of<STENCIL>(need, cell, ix, iy);
-        if (c.valid)
-            for (int64_t r = c.ya; r <= c.yb; ++r) {
-                atomicMin(&rowMin[r - rmin], (int)c.xa);
-                atomicMax(&rowMax[r - rmin], (int)c.xb);
-            }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const int64_t layer = ix * iy;
-        uint32_t acc = 0;
-        for (int i = 0; i < nr; ++i) {
-            rowChunk[i] = acc;
-            if (rowMax[i] >= rowMin[i]) {
-                // the segment starts on a 16-byte boundary of the SLICE (the DMA moves 16 bytes per lane; aligned pieces stay
-                // inside one line): it may begin up to 3 cells before the first cell needed, in the row above for x < 0
-                const int64_t first = (int64_t)(rmin + i) * ix + rowMin[i];
-                int64_t start = first & ~(int64_t)(cpc - 1);
-                const uint32_t nch = (uint32_t)((first - start + (rowMax[i] - rowMin[i])) / cpc + 1);
-                // a last chunk that would cross the end of the slice is moved back instead (unaligned, still whole; slices of
-                // stored types hold a multiple of 4 bytes, so the chunk still starts on a 4-byte boundary)
-                if (start + cpc * (int64_t)nch > layer) start = layer - cpc * (int64_t)nch;
-                if (start < 0) shFail = 1;
-                rowMin[i] = (int)(start - (int64_t)(rmin + i) * ix);  // column of the segment's first cell, may be negative
-                acc += nch;
-            }
+    auto cells = [&](auto&& f) {
+        for (uint32_t e = threadIdx.x; e < nCells; e += kBlock) {
+            const uint32_t y = T.y0 + e / T.w, x = T.x0 + e % T.w;
+            if (y >= outY) continue;
+            const size_t cell = (size_t)y * outX + x;
+            f(cell, need_of<STENCIL>(need, cell, ix, iy));
         }
-        rowChunk[nr] = acc;
-        if (acc > capChunks) shFail = 1;
-    }
-    __syncthreads();
+    };
+    const int nr = fp.scan(cells);
+    const bool fits = nr >= 0 && fp.segments(nr, ix, iy, cpc, capChunks);
     if (!emit) {
-        if (threadIdx.x == 0) tiles[t].nChunks = shFail ? 0xFFFFFFFFu : rowChunk[nr];
+        if (threadIdx.x == 0) tiles[t].nChunks = fits ? fp.rowChunk[nr] : kTileTooLarge;
         return;
     }
-    const uint32_t total = rowChunk[nr];
+    if (nr < 0) return;
+    const uint32_t total = fp.rowChunk[nr];
     for (uint32_t c = threadIdx.x; c < total; c += kBlock) {
         uint32_t lo = 0, hi = (uint32_t)nr - 1;  // last row whose first chunk <= c and that holds chunks
         while (lo < hi) {
             const uint32_t mid = (lo + hi + 1) >> 1;
-            if (rowChunk[mid] <= c) lo = mid; else hi = mid - 1;
+            if (fp.rowChunk[mid] <= c) lo = mid; else hi = mid - 1;
         }
-        chunkOff[T.chunkBase + c] = (uint32_t)((int64_t)(rmin + (int)lo) * ix + rowMin[lo] + cpc * (int64_t)(c - rowChunk[lo]));
+        chunkOff[T.chunkBase + c] = (uint32_t)(fp.segment_start((int)lo, ix) + cpc * (int64_t)(c - fp.rowChunk[lo]));
     }
-    for (uint32_t e = threadIdx.x; e < nCells; e += kBlock) {
-        const uint32_t y = T.y0 + e / T.w, x = T.x0 + e % T.w;
-        if (y >= outY) continue;
-        const size_t cell = (size_t)y * outX + x;
-        const CellNeed c = need_of<STENCIL>(need, cell, ix, iy);
-        uint32_t a = kInvalidPos, b = kInvalidPos;
-        if (c.valid) {
-            uint32_t off[4];
-            for (int r = 0; r < 4; ++r) {
-                const int64_t row = (c.ya + r <= c.yb) ? c.ya + r : c.yb;  // missing rows repeat the last one
-                const int i = (int)(row - rmin);
-                off[r] = rowChunk[i] * cpc + (uint32_t)(c.xa - rowMin[i]);
-            }
-            a = off[0] | (off[1] << 16);
-            b = off[2] | (off[3] << 16);
-        }
+    cells([&](size_t cell, const CellNeed& c) {
+        uint32_t a, b;
+        fp.offsets(c, cpc, a, b);
         ldsA[cell] = a;
         if (STENCIL == 4) ldsB[cell] = b;
-    }
+    });
 }
 
 template <int STENCIL>
@@ -150,34 +94,18 @@ bool build_shape(const fimex_amd_regrid_plan& plan, Staged2Plan& s, const NeedSo
     const uint32_t tileH = sh.tileH;
     const uint32_t nBands = (uint32_t)ceil_div(outY, tileH);
     // the ring holds `depth` slots, each large enough for any tile (chunks rounded up to whole wave instructions)
-    uint32_t cap = std::min<uint32_t>(slot_chunks(sh.ldsBytes, sh.depth), (uint32_t)sh.kmax * sh.nt);
-    cap = std::min<uint32_t>(cap, 65535u / cpc);  // 16-bit LDS offsets, in elements
-    const uint32_t step = sh.tileW >= 128 ? 64u : 32u;  // tile widths are multiples of this (a wave stores 64 consecutive cells)
-    // Tiles: every tile row starts as tiles of the widest shape.  A tile that does not fit (too many chunks for a slot, too
-    // many source rows) makes its row narrower when most tiles of the row fail (the row's cells cover more source: rows near
-    // the pole of the benchmark plan), otherwise it is split in two; at the narrowest width it becomes a gather tile
-    // (rsv[0] = 1: the kernel reads its stencils from memory).  More than 1/8 of the cells that way: no staged plan.
-    const uint32_t widest = std::min(sh.tileW, (outX + step - 1) / step * step);
+    const uint32_t cap = tile_chunk_cap(sh.ldsBytes, sh.depth, (uint32_t)sh.kmax, (uint32_t)sh.nt, cpc);
+    const uint32_t step = tile_width_step(sh.tileW);
+    // Tiles (staged_layout.hpp): every band starts as tiles of the widest shape; the scan counts every tile's chunks, refine_bands
+    // narrows or splits what does not fit, until everything fits or is a gather tile.  Too many cells in gather tiles: no staged plan.
     std::vector<StagedTile> tiles;
     std::vector<uint32_t> bandOf;
-    auto uniform_row = [&](uint32_t b, uint32_t w, std::vector<StagedTile>& out) {
-        for (uint32_t x0 = 0; x0 < outX; x0 += w) {
-            StagedTile t{};
-            t.x0 = x0;
-            t.y0 = b * tileH;
-            t.w = std::min(w, outX - x0);
-            out.push_back(t);
-        }
-    };
     std::vector<std::vector<StagedTile>> rows(nBands);
-    std::vector<uint32_t> rowW(nBands, widest);
-    for (uint32_t b = 0; b < nBands; ++b) uniform_row(b, widest, rows[b]);
+    std::vector<uint32_t> rowW(nBands, widest_tile(sh.tileW, step, outX));
+    for (uint32_t b = 0; b < nBands; ++b) uniform_row(b * tileH, rowW[b], outX, rows[b]);
     DeviceArray<StagedTile> dTiles;
     for (int pass = 0;; ++pass) {
-        tiles.clear();
-        bandOf.clear();
-        for (uint32_t b = 0; b < nBands; ++b)
-            for (const StagedTile& t : rows[b]) { tiles.push_back(t); bandOf.push_back(b); }
+        flatten_bands(rows, tiles, bandOf);
         if (tiles.size() > 0x7FFFFFFFu / 8) return false;
         dTiles.allocate(tiles.size());
         FA_HIP(hipMemcpyAsync(dTiles.get(), tiles.data(), tiles.size() * sizeof(StagedTile), hipMemcpyHostToDevice, stream));
@@ -186,59 +114,12 @@ bool build_shape(const fimex_amd_regrid_plan& plan, Staged2Plan& s, const NeedSo
         FA_HIP(hipGetLastError());
         FA_HIP(hipMemcpyAsync(tiles.data(), dTiles.get(), tiles.size() * sizeof(StagedTile), hipMemcpyDeviceToHost, stream));
         FA_HIP(hipStreamSynchronize(stream));
-        bool again = false;
-        size_t i = 0;
-        for (uint32_t b = 0; b < nBands; ++b) {
-            const size_t n = rows[b].size();
-            size_t failed = 0;
-            for (size_t k = 0; k < n; ++k) {
-                rows[b][k] = tiles[i + k];
-                if (tiles[i + k].rsv[0] == 0 && tiles[i + k].nChunks == 0xFFFFFFFFu) ++failed;
-            }
-            i += n;
-            if (failed == 0) continue;
-            again = true;
-            if (2 * failed > n && rowW[b] > step) {  // the whole row is too heavy: narrower tiles throughout
-                rowW[b] -= step;
-                rows[b].clear();
-                uniform_row(b, rowW[b], rows[b]);
-                continue;
-            }
-            std::vector<StagedTile> next;
-            for (const StagedTile& t : rows[b]) {
-                if (t.rsv[0] != 0 || t.nChunks != 0xFFFFFFFFu) { next.push_back(t); continue; }
-                if (t.w <= step) {  // cannot be split any further
-                    StagedTile g = t;
-                    g.nChunks = 0;
-                    g.rsv[0] = 1;
-                    next.push_back(g);
-                    continue;
-                }
-                StagedTile l = t, r = t;
-                l.w = (t.w / 2 + step - 1) / step * step;
-                r.x0 = t.x0 + l.w;
-                r.w = t.w - l.w;
-                l.nChunks = r.nChunks = 0;
-                next.push_back(l);
-                next.push_back(r);
-            }
-            rows[b].swap(next);
-        }
-        if (!again) break;
+        if (!refine_bands(rows, rowW, step, outX, tiles.data())) break;
         if (pass > 64) return false;
     }
-    size_t gatherCells = 0, liveCells = 0;
-    for (const StagedTile& t : tiles) {
-        if (t.rsv[0] != 0) gatherCells += t.w;
-        if (t.rsv[0] != 0 || t.nChunks != 0) liveCells += t.w;
-    }
-    if (gatherCells * 8 > liveCells) return false;  // positions without spatial coherence: the gather kernels serve them better
+    if (gather_share_too_large(tiles)) return false;
     size_t total = 0;
-    for (auto& t : tiles) {
-        FA_REQUIRE(total <= 0xFFFFFFFFu, "staged plan: too many chunks");
-        t.chunkBase = (uint32_t)total;
-        total += t.nChunks;
-    }
+    FA_REQUIRE(assign_chunk_bases(tiles, total), "staged plan: too many chunks");
     if (total > 0xFFFFFFFFull) return false;
     FA_HIP(hipMemcpyAsync(dTiles.get(), tiles.data(), tiles.size() * sizeof(StagedTile), hipMemcpyHostToDevice, stream));
     const size_t n = plan.outX * plan.outY;
@@ -248,21 +129,7 @@ bool build_shape(const fimex_amd_regrid_plan& plan, Staged2Plan& s, const NeedSo
     tile_scan<STENCIL><<<(uint32_t)tiles.size(), kBlock, 0, stream>>>(need, (int64_t)plan.inX, (int64_t)plan.inY, outX, outY, tileH,
                                                                    dTiles.get(), cap, 1, s.chunkOff.get(), s.ldsA.get(), s.ldsB.get(), cpc);
     FA_HIP(hipGetLastError());
-    // workgroup -> tile: workgroups are dealt round-robin over the XCDs (b % 8 shares an L2); tile rows go to the XCDs in
-    // stripes of `stripe` rows, so that neighbours in x (and, inside a stripe, in y) run on the same XCD and meet in its L2
-    // (stripes of about `stripe` rows, their number a multiple of the XCD count so that every XCD gets equally many)
-    std::vector<std::vector<uint32_t>> perXcd(kXcds);
-    uint32_t nStripes = (uint32_t)((nBands + stripe * kXcds / 2) / (stripe * kXcds)) * kXcds;
-    if (nStripes < (uint32_t)kXcds) nStripes = kXcds;
-    if (nStripes > nBands) nStripes = std::max<uint32_t>(nBands / kXcds * kXcds, 1);
-    // (fewer tile rows than XCDs -- wide, short targets such as cross-sections: the tiles themselves are dealt round-robin)
-    for (size_t i = 0; i < tiles.size(); ++i)
-        perXcd[nBands < (uint32_t)kXcds ? i % kXcds : ((uint64_t)bandOf[i] * nStripes / nBands) % kXcds].push_back((uint32_t)i);
-    size_t longest = 0;
-    for (auto& l : perXcd) longest = std::max(longest, l.size());
-    std::vector<uint32_t> order(longest * kXcds, 0xFFFFFFFFu);
-    for (int x = 0; x < kXcds; ++x)
-        for (size_t k = 0; k < perXcd[x].size(); ++k) order[k * kXcds + x] = perXcd[x][k];
+    const std::vector<uint32_t> order = xcd_order(bandOf, nBands, stripe);  // workgroup -> tile
     s.order.allocate(order.size());
     FA_HIP(hipMemcpyAsync(s.order.get(), order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     FA_HIP(hipStreamSynchronize(stream));

@@ -308,13 +308,8 @@ bool launch_staged2_apply_typed(const fimex_amd_regrid_plan& plan, const void* d
     Staged2Args a = staged2_args(plan, s, d_in, d_out, eb, nz);
     // z chunks of about 50 slices (200 slices: 1.354 against 1.364 ms with 25, profiles/r03_sweep_typed*.log), at least four
     // where the batch allows, so that short batches still fill the chip
-    uint32_t zpb = (uint32_t)tuning("STAGE2T_ZPB", 50);
-    if (zpb < 1) zpb = 1;
-    if (ceil_div(nz, (size_t)zpb) > 16) zpb = (uint32_t)ceil_div(nz, (size_t)16);
-    uint32_t n = (uint32_t)ceil_div(nz, (size_t)zpb);
-    n = std::max<uint32_t>(n, (uint32_t)std::min<size_t>(4, nz / 6));
-    if (n < 1) n = 1;
-    even_z_split(a, nz, n);
+    const uint32_t n = typed_z_chunk_count(nz, (uint32_t)tuning("STAGE2T_ZPB", 50));
+    set_z_chunks(a, even_z_split(nz, n), true);
     TypedEdge te{};
     te.bad = (float)badValue;
     te.hasBad = !(te.bad != te.bad);

@@ -5,12 +5,16 @@
 
 DIR holds libfimex_amd.so built from the commit to compare with; the other side is the library of this tree.  The two sides
 alternate, one fresh process per side and round, each process runs every case: bilinear (the bench.py headline), nearest and
-bicubic in float arithmetic on 200 float slices, bilinear on int16 and nearest on uint8 on 200 slices, bilinear on 25 slices.
+bicubic in float arithmetic on 200 float slices, bilinear on int16 and nearest on uint8 on 200 slices, bilinear on 25 slices, bicubic
+in the reference's arithmetic on 200 slices (the first staged form's production launch), and the creation of the bilinear plan from
+positions on the device (wall time, its host round trips included).  One untimed case hashes what info() says of every plan the
+script builds (planBytes, stagedCells, tileW, tileH, undefined and border cells): equal planBytes means equal tile count, chunk
+total and table length.
 Per case and round the minimum of three timed launches counts, then the median over the rounds.  Margin: new median - parent
 median <= the parent's own (max - min) over its rounds.  A sha256 of the output bytes per case must be the same on both sides in
 every round.  The driver (compare_builds.py) stops at the first process that does not end normally.
 """
-import argparse, hashlib, json, os, sys
+import argparse, hashlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import compare_builds  # beside this script
@@ -52,15 +56,42 @@ def worker():
         d_out = torch.empty((200, wl.outY, wl.outX), dtype=d_in.dtype, device="cuda")
         timed(name, lambda: fa.regrid_apply_typed_device(plan, d_in.data_ptr(), code, 200, bad, d_out.data_ptr(), st), d_out)
 
-    bilinear, _, _ = bench.build_plan(fa, torch, wl, fa.BILINEAR, st)
+    infos = {}
+
+    def built(name, plan):
+        i = plan.info()
+        infos[name] = {k: i[k] for k in ("planBytes", "stagedCells", "tileW", "tileH", "undefinedCells", "borderCells")}
+        return plan
+
+    bilinear, px, py = bench.build_plan(fa, torch, wl, fa.BILINEAR, st)
+    built("bilinear", bilinear)
     floats("bilinear_nz200", bilinear, 200)
     floats("bilinear_nz25", bilinear, 25)
     stored("bilinear_int16_nz200", bilinear, d_i16, fa.CDM_SHORT, -32767.0)
-    nearest, _, _ = bench.build_plan(fa, torch, wl, fa.NEAREST_NEIGHBOR, st)
+    nearest = built("nearest", bench.build_plan(fa, torch, wl, fa.NEAREST_NEIGHBOR, st)[0])
     floats("nearest_nz200", nearest, 200)
     stored("nearest_uint8_nz200", nearest, d_u8, fa.CDM_UCHAR, 255.0)
-    cubic, _, _ = bench.build_plan(fa, torch, wl, fa.BICUBIC, st, bicubic=fa.BICUBIC_FAST)
+    cubic = built("bicubic_float", bench.build_plan(fa, torch, wl, fa.BICUBIC, st, bicubic=fa.BICUBIC_FAST)[0])
     floats("bicubic_float_nz200", cubic, 200)
+    del cubic
+    cubic = built("bicubic_reference", bench.build_plan(fa, torch, wl, fa.BICUBIC, st, bicubic=fa.BICUBIC_REFERENCE)[0])
+    floats("bicubic_reference_nz200", cubic, 200)
+    del cubic
+
+    # plan creation from positions that are on the device already
+    d_px, d_py = torch.from_numpy(px).cuda(), torch.from_numpy(py).cuda()
+    ts = []
+    for k in range(5):  # two untimed
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        plan = fa.RegridPlan.from_device(fa.BILINEAR, d_px.data_ptr(), d_py.data_ptr(), d_px.numel(), wl.inX, wl.inY, wl.outX, wl.outY, st)
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+        built("bilinear_again_%d" % k, plan)
+        del plan
+    print(json.dumps({"case": "bilinear_plan_create", "seconds": ts[2:],
+                      "sha256": hashlib.sha256(json.dumps(infos["bilinear_again_4"], sort_keys=True).encode()).hexdigest()}), flush=True)
+    print(json.dumps({"case": "plan_info", "sha256": hashlib.sha256(json.dumps(infos, sort_keys=True).encode()).hexdigest(), "info": infos}), flush=True)
 
 
 WHAT = "Staged regrid launches on the benchmark geometry."

@@ -5,7 +5,9 @@ thread count, and on stored types single stores, depth 3, a tile row outside the
 Positions are affine maps (px = x * r + ox, py = y * r + oy), so that a tile's footprint can be computed; targets are a few
 tiles.  Everything is compared bit for bit with the oracle, except bicubic in float arithmetic: that one meets the tolerance of
 test_bicubic_fast_arithmetic_within_the_stated_tolerance (1e-5 of the stencil's magnitude, same NaN positions) and its variants
-are bit-equal among themselves.  What test_stored_types_second_staged_form_edges covers (unaligned output, no fill value, fill
+are bit-equal among themselves.  Two tests hold the plans themselves to the CPU: the tile cutting (staged_layout.hpp, driven here with
+a numpy footprint) against the plan the library builds, and the first staged form's footprint on a uniform grid.  What
+test_stored_types_second_staged_form_edges covers (unaligned output, no fill value, fill
 values at the ends of the range) is not repeated here.
 """
 import numpy as np
@@ -30,26 +32,35 @@ def affine(outX, outY, r, ox, oy):
     return (x * r + ox).ravel(), (y * r + oy).ravel()
 
 
-def tile_chunks(stencil, px, py, inX, inY, outX, outY, tw, th, cpc=4):
-    """16-byte chunks per tile as tile_scan counts them on a uniform grid of tw x th tiles whose cells all lie inside the
-    source: per source row the smallest and largest column any cell of the tile needs, the segment's start aligned down to cpc
-    cells of the slice.  (A last chunk past the end of the slice is pulled back, which does not change the count.)"""
+MAX_ROWS = 160  # kMaxRows: source rows one tile may span
+
+
+def tile_list_chunks(stencil, px, py, inX, inY, outX, outY, tiles, cpc=4):
+    """16-byte chunks of each tile (x0, y0, w, h) as the tile footprint (TileFootprint, staged_common.hpp) counts them where all
+    cells lie inside the source: per source row the smallest and largest column any cell of the tile needs, the segment's start
+    aligned down to cpc cells of the slice.  (A last chunk past the end of the slice is pulled back, which does not change the
+    count.)  None: the tile spans more than MAX_ROWS source rows."""
     first = np.floor(px + 0.5) if stencil == 1 else np.floor(px), np.floor(py + 0.5) if stencil == 1 else np.floor(py)
-    xa, ya = (v.astype(np.int64).reshape(outY, outX) for v in first)
+    xa, ya = (v.astype(np.int64).reshape(outY, outX) - (1 if stencil == 4 else 0) for v in first)
     xb, yb = xa + stencil - 1, ya + stencil - 1
     assert xa.min() >= 0 and xb.max() < inX and ya.min() >= 0 and yb.max() < inY
     counts = []
-    for y0 in range(0, outY, th):
-        for x0 in range(0, outX, tw):
-            t = (slice(y0, y0 + th), slice(x0, x0 + tw))
-            n = 0
-            for row in range(ya[t].min(), yb[t].max() + 1):
-                use = (ya[t] <= row) & (row <= yb[t])
-                if use.any():
-                    lo, hi = xa[t][use].min(), xb[t][use].max()
-                    n += ((row * inX + lo) % cpc + hi - lo) // cpc + 1
-            counts.append(n)
+    for x0, y0, w, h in tiles:
+        t = (slice(y0, y0 + h), slice(x0, x0 + w))
+        n = 0
+        for row in range(ya[t].min(), yb[t].max() + 1):
+            use = (ya[t] <= row) & (row <= yb[t])
+            if use.any():
+                lo, hi = xa[t][use].min(), xb[t][use].max()
+                n += ((row * inX + lo) % cpc + hi - lo) // cpc + 1
+        counts.append(int(n) if yb[t].max() - ya[t].min() < MAX_ROWS else None)
     return counts
+
+
+def tile_chunks(stencil, px, py, inX, inY, outX, outY, tw, th, cpc=4):
+    """the same on a uniform grid of tw x th tiles"""
+    return tile_list_chunks(stencil, px, py, inX, inY, outX, outY,
+                            [(x0, y0, tw, th) for y0 in range(0, outY, th) for x0 in range(0, outX, tw)], cpc)
 
 
 def run_float(fa, plan, f, nz, outX, outY):
@@ -136,6 +147,74 @@ def test_every_number_of_dma_rounds(fa, tuning_build, monkeypatch, stencil, k, r
     assert (info["tileW"], info["tileH"]) == (128, 8) and info["stagedCells"] == 4 * sum(counts), (info, counts)
     f = cases.field(3, inY, inX, seed=k, extremes=False)
     want = oracle.interpolate_values(method, px, py, f, inX, inY, outX, outY)
+    got = run_float(fa, plan, f, 3, outX, outY)
+    assert cases.same(got, want), cases.describe_mismatch(got, want)
+
+
+# ---- tile cutting, end to end: the default bilinear shape (1024 threads on 512 x 8 tiles, 5056 chunks per slot) on a map whose
+# bands differ.  Rows 0 .. 31 stretch more and more (1.5 .. 4.4 source columns per output column), rows 32 .. 63 stay at 1.5, and in
+# rows 32 .. 47 the columns from 768 on cover seven source columns each: some bands must narrow, some only split a tile.
+def cutting_case():
+    inX, inY, outX, outY = 4516, 85, 1024, 64
+    y, x = np.meshgrid(np.arange(outY, dtype=np.float64), np.arange(outX, dtype=np.float64), indexing="ij")
+    r = 1.5 + 3.0 * np.minimum(y, 31) / 32
+    r[32:] = 1.5
+    px = x * r + 1.3
+    stretched = (y >= 32) & (y < 48) & (x >= 768)
+    px[stretched] = 1152 + 7 * (x[stretched] - 768) + 1.3
+    return px.ravel(), (1.2 * y + 1.6).ravel(), inX, inY, outX, outY
+
+
+def cut_on_the_cpu(px, py, inX, inY, outX, outY):
+    """refine_bands (staged_layout.hpp) driven by the numpy footprint above, as build_shape drives it with tile_scan"""
+    import staged_layout_host as slh
+    lib = slh.load()
+    cap = lib.sl_tile_chunk_cap(159 * 1024, 2, 5, 1024, 4)
+    assert cap == 5056
+
+    def scan(tiles):
+        counts = tile_list_chunks(2, px, py, inX, inY, outX, outY, [(t.x0, t.y0, t.w, 8) for t in tiles])
+        return [slh.TOO_LARGE if c is None or c > cap else c for c in counts]
+    return slh.cut_tiles(lib, outX, outY, 512, 8, scan)
+
+
+def test_cutting_case_narrows_a_band_and_splits_tiles():
+    """the case does what it is for: some band is narrower than 512, some band keeps its width and holds a split tile, and no tile
+    is left to the gather kernel"""
+    passes, kept, total = cut_on_the_cpu(*cutting_case())
+    last = passes[-1]
+    assert kept and len(passes) > 1 and not any(t.gather for t in last)
+    assert any(t.band_w < 512 for t in last) and any(t.band_w == 512 and t.w < 512 and t.x0 + t.w < 1024 for t in last)
+    print("bands:", {t.band: t.band_w for t in last}, "tiles:", len(last), "staged cells:", 4 * total)
+
+
+@gpu
+def test_tile_cutting_end_to_end(fa, tuning_build, monkeypatch):
+    px, py, inX, inY, outX, outY = cutting_case()
+    passes, kept, total = cut_on_the_cpu(px, py, inX, inY, outX, outY)
+    assert kept
+    monkeypatch.setenv("FIMEX_AMD_STAGED_MIN_NZ", "1")
+    plan = fa.RegridPlan(oracle.BILINEAR, px, py, inX, inY, outX, outY)
+    info = plan.info()
+    assert info["stagedCells"] == 4 * total and info["tileW"] == max(t.w for t in passes[-1]) and info["tileH"] == 8, (info, total)
+    f = cases.field(3, inY, inX, seed=7, extremes=False)
+    want = oracle.interpolate_values(oracle.BILINEAR, px, py, f, inX, inY, outX, outY)
+    got = run_float(fa, plan, f, 3, outX, outY)
+    assert cases.same(got, want), cases.describe_mismatch(got, want)
+
+
+# ---- the first staged form: bicubic in the reference's arithmetic keeps it (32 x 16 tiles of 256 threads, row segments of 4 cells)
+@gpu
+def test_first_form_footprint_and_values(fa, tuning_build, monkeypatch):
+    inX, inY, outX, outY = 96, 52, 64, 32
+    px, py = affine(outX, outY, 1.3, 1.3, 1.6)
+    monkeypatch.setenv("FIMEX_AMD_STAGED_MIN_NZ", "1")
+    plan = fa.RegridPlan(oracle.BICUBIC, px, py, inX, inY, outX, outY, bicubic=fa.BICUBIC_REFERENCE)
+    info = plan.info()
+    counts = tile_chunks(4, px, py, inX, inY, outX, outY, 32, 16, cpc=4)
+    assert len(counts) == 4 and (info["tileW"], info["tileH"]) == (32, 16) and info["stagedCells"] == 4 * sum(counts), (info, counts)
+    f = cases.field(3, inY, inX, seed=9, extremes=False)
+    want = oracle.interpolate_values(oracle.BICUBIC, px, py, f, inX, inY, outX, outY)
     got = run_float(fa, plan, f, 3, outX, outY)
     assert cases.same(got, want), cases.describe_mismatch(got, want)
 
