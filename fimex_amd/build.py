@@ -26,7 +26,7 @@ PROJECTION_SHIM = os.path.join(ROOT, "tests", "projection_host.hip")
 FORWARD_MATH_LIB = os.path.join(HERE, "libforward_math_host.so")  # csrc/forward_math.hpp compiled for the CPU (tests/test_forward_math_host.py)
 FORWARD_MATH_SHIM = os.path.join(ROOT, "tests", "forward_math_host.hip")
 
-DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
+DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "staged2_vector_typed.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "scaled_convert.hip", "pressure_convert.hip",
                   "time_accumulate.hip", "time_interpolate.hip", "quality.hip", "extract.hip", "vertical_plan.hip"]
 
 # -ffp-contract=off: the kernels reproduce the reference's IEEE arithmetic operation by operation
@@ -50,7 +50,7 @@ def _newer(target, deps):
 
 def _headers():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    hdrs += [os.path.join(ROOT, "include", h) for h in ("fimex_amd.h", "fimex_amd_derived_host.h", "fimex_amd_time_quality_host.h", "fimex_amd_extract_host.h", "fimex_amd_vertical_plan_host.h", "fimex_amd_vector_regrid_host.h")]
+    hdrs += [os.path.join(ROOT, "include", h) for h in ("fimex_amd.h", "fimex_amd_derived_host.h", "fimex_amd_time_quality_host.h", "fimex_amd_extract_host.h", "fimex_amd_vertical_plan_host.h", "fimex_amd_vector_regrid_host.h", "fimex_amd_vector_regrid_typed_host.h")]
     return hdrs
 
 

@@ -135,6 +135,8 @@ SYMBOLS = {
     "fimex_amd_data2interpolation_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, ctypes.c_double, _V, _V]),
     "fimex_amd_interpolation2data_device": (ctypes.c_int, [_V, _Z, ctypes.c_int, ctypes.c_double, _V, _V]),
     "fimex_amd_regrid_apply_typed_device": (ctypes.c_int, [_V, _V, ctypes.c_int, _Z, ctypes.c_double, _V, _V]),
+    "fimex_amd_regrid_apply_vector_typed_device": (ctypes.c_int, [_V, _V, _V, ctypes.c_int, ctypes.c_double, _V, ctypes.c_int, ctypes.c_double, _Z,
+                                                                  _V, _V, _V, ctypes.POINTER(ctypes.c_int)]),
     "fimex_amd_data2interpolation_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, ctypes.c_double, _F]),
     "fimex_amd_interpolation2data_host": (ctypes.c_int, [_F, _Z, ctypes.c_int, ctypes.c_double, _V]),
     "fimex_amd_regrid_slice_typed_host": (ctypes.c_int, [_V, _V, ctypes.c_int, _Z, ctypes.c_double, ctypes.POINTER(Process2d), _Z,
@@ -247,6 +249,12 @@ VECTOR_REGRID_HOST_SYMBOLS = {
     "fimex_amd_regrid_apply_vector_host": (ctypes.c_int, [_V, _V, _F, _F, _Z, _F, _F, _Z, _ZP]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_vector_regrid_typed_host.h declares: a vector pair in its stored types on host buffers
+VECTOR_REGRID_TYPED_HOST_SYMBOLS = {
+    "fimex_amd_regrid_apply_vector_typed_host": (ctypes.c_int, [_V, _V, _V, ctypes.c_int, ctypes.c_double, _V, ctypes.c_int, ctypes.c_double, _Z,
+                                                                _V, _V, _Z, _ZP]),
+}
+
 # name -> (restype, argtypes); every symbol include/fimex_amd_vertical_plan_host.h declares: the entries of (8f n5b) on host buffers
 VERTICAL_PLAN_HOST_SYMBOLS = {
     "fimex_amd_vertical_plan_create_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, ctypes.POINTER(VerticalLevelsStruct),
@@ -270,7 +278,8 @@ def _open(path):
         pass
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
-            EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()) + list(VECTOR_REGRID_HOST_SYMBOLS.items()):
+            EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()) + list(VECTOR_REGRID_HOST_SYMBOLS.items()) + list(
+            VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -404,6 +413,28 @@ class RegridPlan:
         uOut, vOut = (np.empty(nz * self.outX * self.outY, dtype=np.float32) for _ in range(2))
         n = _Z(0)
         _check(load().fimex_amd_regrid_apply_vector_host(self._h, vec._h, _fp(a), _fp(b), a.size, _fp(uOut), _fp(vOut), uOut.size, ctypes.byref(n)))
+        return uOut.reshape(-1, self.outY, self.outX), vOut.reshape(-1, self.outY, self.outX)
+
+    def apply_vector_typed_device(self, vec, d_u, uType, uBad, d_v, vType, vBad, nz, d_uOut, d_vOut, stream=0):
+        """The same on a pair in its stored types (CDM_* codes; each component with its own type and fill value, results in the
+        same types).  Returns the path: 2 one kernel on the stored type, 1 or 0 the chain around apply_vector_device."""
+        path = ctypes.c_int(-1)
+        _check(load().fimex_amd_regrid_apply_vector_typed_device(self._h, vec._h, d_u, uType, uBad, d_v, vType, vBad, nz, d_uOut, d_vOut, stream,
+                                                                 ctypes.byref(path)))
+        return path.value
+
+    def apply_vector_typed_host(self, vec, u, uBad, v, vBad):
+        """The same on [nz][inY][inX] host arrays of any numeric CDM type; returns (uOut, vOut), each [nz][outY][outX] in the dtype
+        of its component."""
+        a, b = np.ascontiguousarray(u).ravel(), np.ascontiguousarray(v).ravel()
+        if a.size != b.size:
+            raise ValueError("the components differ in size")
+        nz = a.size // (self.inX * self.inY) if self.inX * self.inY else 0
+        uOut, vOut = np.empty(nz * self.outX * self.outY, dtype=a.dtype), np.empty(nz * self.outX * self.outY, dtype=b.dtype)
+        n = _Z(0)
+        _check(load().fimex_amd_regrid_apply_vector_typed_host(self._h, vec._h, a.ctypes.data, cdm_type_of(a.dtype), uBad, b.ctypes.data,
+                                                               cdm_type_of(b.dtype), vBad, a.size, uOut.ctypes.data, vOut.ctypes.data, uOut.size,
+                                                               ctypes.byref(n)))
         return uOut.reshape(-1, self.outY, self.outX), vOut.reshape(-1, self.outY, self.outX)
 
     def apply_gather_device(self, d_in, nz, d_out, stream=0):

@@ -1,10 +1,12 @@
 // extern "C" boundary, vectors and projections: the vector reprojection plan and its applies (vector.hip), the proj-level entries
 // (projection.hip), the coordinate searches (coordsearch.hip), points2position (convert.hip), and the regrid of a vector pair
-// with its rotation (staged2_vector.hip, or the three launches it replaces).
+// with its rotation (staged2_vector.hip, or the three launches it replaces), on float slices and on the pair's stored types
+// (staged2_vector_typed.hip, or the five launches it replaces).
 #include "capi_checks.hpp"
 #include "host_call.hpp"
 
 #include "../../include/fimex_amd_vector_regrid_host.h"
+#include "../../include/fimex_amd_vector_regrid_typed_host.h"
 
 #include <memory>
 #include <string>
@@ -59,21 +61,28 @@ void check_coord_search_host(const double* px, const double* py, size_t nPoints,
     FA_REQUIRE(n == 0 || (lon != nullptr && lat != nullptr), "NULL argument");
 }
 
-// what both forms of regrid_apply_vector refuse; the buffers are the caller's own pointers, host or device
-void check_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* u, const float* v, size_t nz,
-                       const float* uOut, const float* vOut)
+// what every form of regrid_apply_vector refuses; the buffers are the caller's own pointers, host or device, and their sizes count
+// elements of uElem bytes (u, uOut) and vElem bytes (v, vOut)
+void check_vector_pair_sized(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* u, size_t uElem, const void* v,
+                             size_t vElem, size_t nz, const void* uOut, const void* vOut)
 {
     FA_REQUIRE(plan.kind != PlanKind::Forward, "a vector pair is regridded with a backward plan, this is a forward plan");
     FA_REQUIRE(vec.ox == plan.outX && vec.oy == plan.outY, "the vector plan's grid (ox, oy) differs from the regrid plan's output grid (outX, outY)");
     FA_REQUIRE(vec.device == plan.device, "the regrid plan and the vector plan live on different devices");
-    const size_t inBytes = nz * plan.inX * plan.inY * sizeof(float), outBytes = nz * plan.outX * plan.outY * sizeof(float);
-    const Span b[4] = {{u, inBytes, "u"}, {v, inBytes, "v"}, {uOut, outBytes, "uOut"}, {vOut, outBytes, "vOut"}};
+    const size_t inCells = nz * plan.inX * plan.inY, outCells = nz * plan.outX * plan.outY;
+    const Span b[4] = {{u, inCells * uElem, "u"}, {v, inCells * vElem, "v"}, {uOut, outCells * uElem, "uOut"}, {vOut, outCells * vElem, "vOut"}};
     for (int i = 0; i < 4; ++i)
         for (int j = i + 1; j < 4; ++j) {
             const char *p = static_cast<const char*>(b[i].p), *q = static_cast<const char*>(b[j].p);
             FA_REQUIRE(!b[i].bytes || !b[j].bytes || p + b[i].bytes <= q || q + b[j].bytes <= p,
                        std::string("buffers overlap: ") + b[i].name + " and " + b[j].name);
         }
+}
+
+void check_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* u, const float* v, size_t nz,
+                       const float* uOut, const float* vOut)
+{
+    check_vector_pair_sized(plan, vec, u, sizeof(float), v, sizeof(float), nz, uOut, vOut);
 }
 
 // CDMInterpolator.cc:259-277 on device buffers: the fused kernel where it serves the plan and the batch, else the chain it
@@ -89,6 +98,24 @@ int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_
     apply_plan_device(plan, d_v, nz, d_vOut, stream);
     launch_vector_values(vec, d_uOut, d_vOut, nz, stream);
     return 0;
+}
+
+// CDMInterpolator.cc:251-285 on device buffers in the components' stored types: the kernel on the stored type (path 2) where it
+// serves the pair, else the chain it replaces -- to float, the float pair, back to the stored types -- on temporaries that are
+// released after the stream has been waited for; returns the path taken (the chain: what apply_vector_pair took)
+int apply_vector_pair_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, int uType, double uBad,
+                            const void* d_v, int vType, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream)
+{
+    if (uType == vType && launch_staged2_apply_vector_typed(plan, vec, d_u, d_v, uType, uBad, vBad, nz, d_uOut, d_vOut, stream)) return 2;
+    const size_t nIn = nz * plan.inX * plan.inY, nOut = nz * plan.outX * plan.outY;
+    DeviceArray<float> fu(nIn), fv(nIn), fuOut(nOut), fvOut(nOut);
+    launch_data2interpolation(d_u, uType, nIn, uBad, fu.get(), stream);
+    launch_data2interpolation(d_v, vType, nIn, vBad, fv.get(), stream);
+    const int taken = apply_vector_pair(plan, vec, fu.get(), fv.get(), nz, fuOut.get(), fvOut.get(), stream);
+    launch_interpolation2data(fuOut.get(), nOut, uType, uBad, d_uOut, stream);
+    launch_interpolation2data(fvOut.get(), nOut, vType, vBad, d_vOut, stream);
+    FA_HIP(hipStreamSynchronize(stream));  // the temporaries are released on return
+    return taken;
 }
 
 }  // namespace
@@ -182,6 +209,49 @@ int fimex_amd_regrid_apply_vector_host(const fimex_amd_regrid_plan* plan, const 
         HostCall hc;
         const float *d_u = hc.in(u, nz * inLayer), *d_v = hc.in(v, nz * inLayer);
         apply_vector_pair(*plan, *vec, d_u, d_v, nz, hc.out(uOut, nz * outLayer), hc.out(vOut, nz * outLayer), hc.stream());
+        hc.finish();
+    });
+}
+
+int fimex_amd_regrid_apply_vector_typed_device(const fimex_amd_regrid_plan* plan, const fimex_amd_vector_plan* vec, const void* d_u, int uType,
+                                               double uBad, const void* d_v, int vType, double vBad, size_t nz, void* d_uOut, void* d_vOut,
+                                               void* stream, int* path)
+{
+    return c_guard([&] {
+        if (path) *path = 0;
+        FA_REQUIRE(plan != nullptr, "NULL regrid plan");
+        FA_REQUIRE(vec != nullptr, "NULL vector plan");
+        const size_t uElem = cdm_type_size(uType), vElem = cdm_type_size(vType);  // throws for NAT and STRING
+        FA_REQUIRE(nz == 0 || (d_u != nullptr && d_v != nullptr && d_uOut != nullptr && d_vOut != nullptr), "NULL device buffer");
+        check_vector_pair_sized(*plan, *vec, d_u, uElem, d_v, vElem, nz, d_uOut, d_vOut);
+        if (nz == 0) return;
+        require_current_device(plan->device);
+        const int taken = apply_vector_pair_typed(*plan, *vec, d_u, uType, uBad, d_v, vType, vBad, nz, d_uOut, d_vOut, as_stream(stream));
+        if (path) *path = taken;
+    });
+}
+
+int fimex_amd_regrid_apply_vector_typed_host(const fimex_amd_regrid_plan* plan, const fimex_amd_vector_plan* vec, const void* u, int uType,
+                                             double uBad, const void* v, int vType, double vBad, size_t size, void* uOut, void* vOut,
+                                             size_t outCapacity, size_t* newSize)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr, "NULL regrid plan");
+        FA_REQUIRE(vec != nullptr, "NULL vector plan");
+        FA_REQUIRE(newSize != nullptr, "NULL argument");
+        const size_t uElem = cdm_type_size(uType), vElem = cdm_type_size(vType);  // throws for NAT and STRING
+        const size_t inLayer = plan->inX * plan->inY, outLayer = plan->outX * plan->outY;
+        const size_t nz = inLayer ? size / inLayer : 0;  // CachedInterpolation.cc:121
+        *newSize = outLayer * nz;                         // :122
+        FA_REQUIRE(nz == 0 || (u != nullptr && v != nullptr && uOut != nullptr && vOut != nullptr), "NULL buffer");
+        check_vector_pair_sized(*plan, *vec, u, uElem, v, vElem, nz, uOut, vOut);
+        if (nz == 0) return;
+        FA_REQUIRE(outCapacity >= *newSize, "output buffers too small");
+        ScopedDevice dev(plan->device);
+        HostCall hc;  // only stored-type bytes cross to the device and back
+        const void *d_u = hc.in_bytes(u, nz * inLayer * uElem), *d_v = hc.in_bytes(v, nz * inLayer * vElem);
+        apply_vector_pair_typed(*plan, *vec, d_u, uType, uBad, d_v, vType, vBad, nz, hc.out_bytes(uOut, nz * outLayer * uElem),
+                                hc.out_bytes(vOut, nz * outLayer * vElem), hc.stream());
         hc.finish();
     });
 }

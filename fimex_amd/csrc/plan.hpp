@@ -174,6 +174,12 @@ void launch_staged2_apply_vector(const fimex_amd_regrid_plan& plan, const fimex_
 bool launch_staged2_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                 hipStream_t stream);
 
+// staged2_vector_typed.hip: a vector pair on its stored type (short / unsigned short, both components in one type) regridded and
+// rotated in one launch; false: not served, nothing launched (other types, plans without the 2-byte form, unaligned sources,
+// batches below staged_min_nz(), switched off in the tuning build)
+bool launch_staged2_apply_vector_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, const void* d_v,
+                                       int cdmType, double uBad, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream);
+
 // forward_plan.hip
 void build_forward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
 // forward.hip (the medians of medium buckets: forward_median.hip, declared in forward.hpp)

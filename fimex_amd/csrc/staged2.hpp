@@ -1,5 +1,6 @@
 // Second LDS-staged regrid form, what its three translation units share: staged2_plan.hip (tile scan, shape choice, plan),
-// staged2.hip (float kernel and launch), staged2_typed.hip (stored-type kernel, form cache and launch).
+// staged2.hip (float kernel and launch), staged2_typed.hip (stored-type kernel, form cache and launch), staged2_vector.hip and
+// staged2_vector_typed.hip (the pair kernels on float slices and on stored types).
 #pragma once
 
 #include "plan.hpp"
@@ -35,6 +36,10 @@ inline bool finish_shape(Shape2& sh, uint32_t widthStep)
 // from the gather plan the positions were turned into.  false: no staged form (positions without spatial coherence).
 bool build_staged2_form(const fimex_amd_regrid_plan& plan, Staged2Plan& form, const double* d_px, const double* d_py, const Shape2& sh,
                         uint32_t stripe, uint32_t cpc, hipStream_t stream);
+
+// staged2_typed.hip: the plan's staged form for slices of elemBytes-byte elements (2 or 1), built on first use and kept with the
+// plan; nullptr: none.  The stored-type kernel and the stored-type pair kernel (staged2_vector_typed.hip) run on it.
+const Staged2Plan* staged2_typed_form(const fimex_amd_regrid_plan& plan, uint32_t elemBytes, hipStream_t stream);
 
 namespace {
 

@@ -1,5 +1,5 @@
 // The shell of the second staged form's kernels (staged2.hip: float slices, staged2_typed.hip: stored 1- and 2-byte types,
-// staged2_vector.hip: pairs of vector components, regridded and rotated): which
+// staged2_vector.hip, staged2_vector_typed.hip: pairs of vector components, regridded and rotated): which
 // tile and z chunk a workgroup owns, the per-lane staging list, the ring of LDS slots that slice z + 1 .. z + DEPTH - 1 stream
 // into by LDS-DMA while slice z is interpolated, and the choice of the loop copy.  The kernels keep what differs: element size,
 // per-lane plan layout, stencil reads and conversions, result stores.
@@ -70,19 +70,20 @@ struct SliceRing {
     uint32_t slotChunks, slotFloats, waveChunk;
     const char* inBaseV = nullptr;  // pairs only (run_pairs): the second component's source
 
-    // The ring of a component pair (staged2_vector.hip): float slices, [z0, z1) counts pairs, and the ring walks the 2 * (z1 - z0)
+    // The ring of a component pair (staged2_vector.hip: float slices; staged2_vector_typed.hip: slices of elemBytes-byte elements,
+    // both components in one type): [z0, z1) counts pairs, and the ring walks the 2 * (z1 - z0)
     // logical slices u(z0), v(z0), u(z0 + 1), ... -- logical slice l is slice z0 + l / 2 of `a.in` (l even) or of `inV` (l odd).
-    __device__ __forceinline__ SliceRing(const Staged2Args& a, const StagedTile& T, uint32_t z0_, uint32_t z1_, const float* inV)
+    __device__ __forceinline__ SliceRing(const Staged2Args& a, const StagedTile& T, uint32_t z0_, uint32_t z1_, const void* inV, uint32_t elemBytes)
         : inBase(reinterpret_cast<const char*>(a.in)), outBase(reinterpret_cast<char*>(a.out)), inBytes(a.inBytes),
-          outBytes(a.nOut * 4u), inRecords((kTuningBuild && (a.flags & 1)) ? 0u : a.inBytes),
-          outRecords((kTuningBuild && (a.flags & 2)) ? 0u : a.nOut * 4u), z0(z0_), z1(z1_), un((T.nChunks + NT - 1) / NT),
+          outBytes(a.nOut * elemBytes), inRecords((kTuningBuild && (a.flags & 1)) ? 0u : a.inBytes),
+          outRecords((kTuningBuild && (a.flags & 2)) ? 0u : a.nOut * elemBytes), z0(z0_), z1(z1_), un((T.nChunks + NT - 1) / NT),
           slotChunks(a.slotChunks), slotFloats(a.slotChunks * 4u), waveChunk((threadIdx.x / kWave) * kWave),
           inBaseV(reinterpret_cast<const char*>(inV))
     {
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) {
             const uint32_t c = threadIdx.x + j * NT;
-            gOff[j] = (c < T.nChunks) ? a.chunkOff[T.chunkBase + c] * 4u : 0xFFFFFFFFu;
+            gOff[j] = (c < T.nChunks) ? a.chunkOff[T.chunkBase + c] * elemBytes : 0xFFFFFFFFu;
         }
         for (uint32_t l = 0; l + 1 < (uint32_t)DEPTH && l < 2 * (z1 - z0); ++l) {
             const rsrc_t rs = in_pair(l);
@@ -181,15 +182,16 @@ struct SliceRing {
 
     // run() for a pair ring (see the pair constructor), one trip per pair with its u step and its v step written out, so that
     // every wait keeps an immediate.  uBody(slot) interpolates the u slice into registers and issues no memory instruction that
-    // counts in vmcnt; vBody(z, slot) interpolates the v slice, rotates and issues exactly 2 * PER stores.  Logical slice l lies in
-    // slot l % DEPTH.  With S(l) the stores of logical step l (0 on a u step, 2 * PER on a v step), this was issued behind the DMA
+    // counts in vmcnt; vBody(z, slot) interpolates the v slice, rotates and issues exactly STORES store instructions (2 * PER in
+    // the float kernel; 2 * NST on stored types, NST = 2 with pair stores and 4 without).  Logical slice l lies in
+    // slot l % DEPTH.  With S(l) the stores of logical step l (0 on a u step, STORES on a v step), this was issued behind the DMA
     // of logical slice l + 1 when step l ends and may stay in flight, by run()'s own argument:
-    //   DEPTH 2  that DMA is issued in step l itself, ahead of the step's stores: S(l), 0 after a u step, 2 * PER after a v step;
+    //   DEPTH 2  that DMA is issued in step l itself, ahead of the step's stores: S(l), 0 after a u step, STORES after a v step;
     //   DEPTH 3  it is issued in step l - 1, then come S(l - 1), the DMA of slice l + 2 (UN instructions) and S(l); one of two
-    //            consecutive steps is a v step: UN + 2 * PER after either;
+    //            consecutive steps is a v step: UN + STORES after either;
     //   tail     the steps that fetch nothing more (DEPTH 3: both steps of the last pair; DEPTH 2: its v step -- the u step still
-    //            fetches the pair's own v slice) leave only their own stores outstanding, 0 and 2 * PER.
-    template <int UN, int PER, class UBody, class VBody>
+    //            fetches the pair's own v slice) leave only their own stores outstanding, 0 and STORES.
+    template <int UN, int STORES, class UBody, class VBody>
     __device__ __forceinline__ void run_pairs(UBody&& uBody, VBody&& vBody) const
     {
         static_assert(DEPTH == 2 || DEPTH == 3, "the slots of a pair's steps are written out for these depths");
@@ -209,15 +211,15 @@ struct SliceRing {
             if (DEPTH == 2) fetch(2 * p + 1, slotV);    // into the slot the v slice of pair p - 1 has left
             else if (more) fetch(2 * p + 2, slotN);
             uBody(reinterpret_cast<const char*>(smem + slotU * slotFloats));
-            if (DEPTH == 3 && more) wait_vmcnt_and_lds<UN + 2 * PER>();
+            if (DEPTH == 3 && more) wait_vmcnt_and_lds<UN + STORES>();
             else wait_vmcnt_and_lds<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             // v step, logical slice 2p + 1
             if (more) fetch(2 * p + DEPTH, slotU);  // into the slot the u slice has just left
             vBody(z0 + p, reinterpret_cast<const char*>(smem + slotV * slotFloats));
-            if (more) wait_vmcnt<(DEPTH - 2) * UN + 2 * PER>();
-            else wait_vmcnt<2 * PER>();
+            if (more) wait_vmcnt<(DEPTH - 2) * UN + STORES>();
+            else wait_vmcnt<STORES>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             slotU = DEPTH == 2 ? slotU : slotN;

@@ -5,9 +5,9 @@
 // the tile, and the same NT * 2 cells further on), so that two results leave in one 4-byte (2-byte elements) or 2-byte store
 // and a wave still writes 256 (128) contiguous bytes; the two source elements of a stencil row arrive in one ds_read2_b32 and
 // are shifted apart; elements become float / NaN as Data::asFloat + mifi_bad2nanf do, results go back through ScaleValue's
-// rounding (typed_convert.hpp).
+// rounding (typed_convert.hpp); the element reads and the stores are staged2_lane_ops.hpp's.
+#include "staged2_lane_ops.hpp"
 #include "staged2_ring.hpp"
-#include "typed_convert.hpp"
 
 namespace fimex_amd {
 
@@ -19,74 +19,6 @@ struct TypedEdge {
     double fillOut;     // NaN -> this (interpolationArray2Data)
     uint32_t pairStore; // outX even: the two results of a pair share one store
 };
-
-template <typename T>
-__device__ __forceinline__ float lds_one(const char* buf, uint32_t byteOff, float bad, bool hasBad)
-{
-    return as_float_nan(*reinterpret_cast<const T*>(buf + byteOff), bad, hasBad);
-}
-// two neighbouring 1- or 2-byte elements at element offset `byteOff / sizeof(T)` of the staged image
-// (alignedOff = byteOff & ~3; shift = byteOff * 8: v_alignbit_b32 takes the low five bits, (byteOff & 3) * 8 -- both are
-// computed once per lane, outside the slice loop),
-// as they are stored, converted but not yet compared with the fill value (the interior form tests all four
-// stencil values at once: any fill value among them makes the result undefined, whatever its weight -- 0 * NaN is NaN)
-template <typename T>
-__device__ __forceinline__ void lds_pair2_raw(const char* buf, uint32_t alignedOff, uint32_t shift, float& first, float& second)
-{
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(buf + alignedOff);
-    const uint32_t both = __builtin_amdgcn_alignbit(w[1], w[0], shift);
-    if constexpr (sizeof(T) == 2) {
-        first = (float)(T)(unsigned short)(both & 0xffffu);
-        second = (float)(T)(unsigned short)(both >> 16);
-    } else {
-        first = (float)(T)(unsigned char)(both & 0xffu);
-        second = (float)(T)(unsigned char)((both >> 8) & 0xffu);
-    }
-}
-template <typename T>
-__device__ __forceinline__ void lds_pair2(const char* buf, uint32_t alignedOff, uint32_t shift, float bad, bool hasBad, float& first, float& second)
-{
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(buf + alignedOff);
-    const uint32_t both = __builtin_amdgcn_alignbit(w[1], w[0], shift);
-    if constexpr (sizeof(T) == 2) {
-        first = as_float_nan((T)(unsigned short)(both & 0xffffu), bad, hasBad);
-        second = as_float_nan((T)(unsigned short)(both >> 16), bad, hasBad);
-    } else {
-        first = as_float_nan((T)(unsigned char)(both & 0xffu), bad, hasBad);
-        second = as_float_nan((T)(unsigned char)((both >> 8) & 0xffu), bad, hasBad);
-    }
-}
-// interpolationArray2Data for results of THIS kernel: NaN -> fill, else MetNoFimex::round (lround) and the reference's casts
-// long -> int -> T (typed_convert.hpp: from_float_fill).  The results here are stored elements or convex combinations of four
-// of them, so |v| < 2^17: the branch of from_float_fill for values beyond the int range cannot be taken and is left out, the
-// rest is the same arithmetic without branches (the fraction v - trunc(v) is exact in float).
-template <typename T>
-__device__ __forceinline__ uint32_t round_bits(float v, T fill)
-{
-    const float t = truncf(v);
-    const float r = t + ((fabsf(v - t) >= 0.5f) ? copysignf(1.f, v) : 0.f);
-    const int i = (v != v) ? (int)fill : (int)r;
-    return (uint32_t)i;
-}
-// results r0 (cell c) and r1 (cell c + 1) of one pair; offsets in BYTES of the typed slice, ~0u = not mine
-constexpr int kTypedStoreAux = 2;  // non-temporal (written through as well -- sc1 nt, the float kernel's policy -- these 4-byte-per-lane stores of half as many bytes lose 9 %: 1.48 against 1.35 ms)
-template <typename T, bool PAIR>
-__device__ __forceinline__ void store_pair(rsrc_t ro, uint32_t off0, uint32_t off1, float r0, float r1, T fill)
-{
-    constexpr uint32_t kMask = sizeof(T) == 2 ? 0xffffu : 0xffu;
-    const uint32_t b0 = round_bits<T>(r0, fill) & kMask, b1 = round_bits<T>(r1, fill) & kMask;
-    if constexpr (PAIR) {  // both cells exist or neither (even row length, even tile widths)
-        if constexpr (sizeof(T) == 2) __builtin_amdgcn_raw_buffer_store_b32(b0 | (b1 << 16), ro, off0, 0, kTypedStoreAux);
-        else __builtin_amdgcn_raw_buffer_store_b16((unsigned short)(b0 | (b1 << 8)), ro, off0, 0, 2);
-        (void)off1;
-    } else if constexpr (sizeof(T) == 2) {
-        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)b0, ro, off0, 0, 2);
-        __builtin_amdgcn_raw_buffer_store_b16((unsigned short)b1, ro, off1, 0, 2);
-    } else {
-        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)b0, ro, off0, 0, 2);
-        __builtin_amdgcn_raw_buffer_store_b8((unsigned char)b1, ro, off1, 0, 2);
-    }
-}
 
 // STENCIL 1 (nearest) or 2 (bilinear); NT threads, 4 outputs per lane (two pairs); KMAX 16-byte chunks per lane and slice
 // PAIR: the row length and the slice start allow aligned stores of two results
@@ -233,6 +165,8 @@ __global__ void __launch_bounds__(NT) staged_apply2_typed(Staged2Args a, TypedEd
     });
 }
 
+}  // namespace
+
 // the plan's staged form for slices of elemBytes-byte elements (2 or 1), built on first use; nullptr: none (the caller takes
 // the first staged form or the gather kernels)
 const Staged2Plan* staged2_typed_form(const fimex_amd_regrid_plan& plan, uint32_t elemBytes, hipStream_t stream)
@@ -263,6 +197,8 @@ const Staged2Plan* staged2_typed_form(const fimex_amd_regrid_plan& plan, uint32_
     }
     return form.valid ? &form : nullptr;
 }
+
+namespace {
 
 template <int STENCIL, typename T>
 void launch_typed_shape(const Staged2Plan& s, const Staged2Args& a, const TypedEdge& te, dim3 grid, hipStream_t stream)

@@ -3,6 +3,7 @@
 // CDMInterpolator::getDataSlice's vector branch (src/CDMInterpolator.cc:259-277: interpolateValues on both components, then
 // CachedVectorReprojection::reprojectValues) in one launch instead of three.  Nearest and bilinear plans; the plan is the one
 // staged_apply2 (staged2.hip) runs, and so are tiles, chunk lists, LDS offsets, workgroup shapes and z chunks.
+#include "staged2_lane_ops.hpp"
 #include "staged2_ring.hpp"
 
 namespace fimex_amd {
@@ -16,15 +17,6 @@ struct Staged2VectorArgs {
     const double2* cs;  // (m0, m1) of the rotation matrix per output cell
 };
 
-// src/interpolation.c:796-810 on one cell, as rotate() of vector.hip: float -> double products, one double add / sub, -> float
-__device__ __forceinline__ void rotate_pair(float u, float v, double c, double s, float& uOut, float& vOut)
-{
-    const double un = (double)u * c - (double)v * s;  // :804
-    const double vn = (double)u * s + (double)v * c;  // :805
-    uOut = (float)un;
-    vOut = (float)vn;
-}
-
 // STENCIL: 1 nearest, 2 bilinear; NT, PER, KMAX, DEPTH as staged_apply2
 template <int STENCIL, int NT, int PER, int KMAX, int DEPTH>
 __global__ void __launch_bounds__(NT) staged_apply2_vector(Staged2VectorArgs va)
@@ -34,7 +26,7 @@ __global__ void __launch_bounds__(NT) staged_apply2_vector(Staged2VectorArgs va)
     StagedTile T;
     uint32_t z0, z1;
     if (!decode_workgroup(a, T, z0, z1)) return;
-    const SliceRing<NT, KMAX, DEPTH> ring(a, T, z0, z1, va.inV);
+    const SliceRing<NT, KMAX, DEPTH> ring(a, T, z0, z1, va.inV, 4u);
     char* const outBaseV = reinterpret_cast<char*>(va.outV);
     // ---- per-lane plan, as staged_apply2; and the rotation of the lane's outputs, held over the z chunk (a load inside the
     // loop would count in vmcnt)
@@ -156,7 +148,7 @@ __global__ void __launch_bounds__(NT) staged_apply2_vector(Staged2VectorArgs va)
             }
         };
         float u[PER];  // the u step's results wait here for the v step: with DEPTH 2 their slot is refilled meanwhile
-        ring.template run_pairs<decltype(unTag)::value, PER>(
+        ring.template run_pairs<decltype(unTag)::value, 2 * PER>(
             [&](const char* curb) __attribute__((always_inline)) { interpolate(curb, u); },
             [&](uint32_t z, const char* curb) __attribute__((always_inline)) {
                 float v[PER];

@@ -239,6 +239,21 @@ int fimex_amd_vector_reproject_direction_device(const fimex_amd_vector_plan* pla
 int fimex_amd_regrid_apply_vector_device(const fimex_amd_regrid_plan* plan, const fimex_amd_vector_plan* vec,
                                          const float* d_u, const float* d_v, size_t nz,
                                          float* d_uOut, float* d_vOut, void* stream, int* path);
+/** The same on a pair in its stored types (src/CDMInterpolator.cc:251-285 without pre- and post-processes, both components at
+ *  once): each component is read as data2InterpolationArray reads it (Data::asFloat, then mifi_bad2nanf with its own fill
+ *  value), both are regridded and rotated, and each comes back as interpolationArray2Data(own type, own fill value).
+ *  d_u, d_uOut hold elements of uType, d_v, d_vOut of vType (fimex_amd_datatype, all ten numeric types; the two may differ);
+ *  layouts, plans and refusals as above, with buffer sizes counted in each buffer's own element size.
+ *  *path (NULL allowed): 2 one kernel on the stored type, no float copy of a slice (both components SHORT or both USHORT,
+ *  nearest and bilinear plans whose source slice is a multiple of 4 bytes and that hold a staged form for 2-byte elements,
+ *  4-byte aligned d_u and d_v, four pairs and more); 1 or 0 the chain of five launches around the float pair entry -- to
+ *  float twice, fimex_amd_regrid_apply_vector_device (whose path this is), back twice -- on temporaries of
+ *  2*4*nz*(inX*inY + outX*outY) bytes, released after a stream synchronisation.  The same bytes either way.
+ *  The *_host form is declared in fimex_amd_vector_regrid_typed_host.h. */
+int fimex_amd_regrid_apply_vector_typed_device(const fimex_amd_regrid_plan* plan, const fimex_amd_vector_plan* vec,
+                                               const void* d_u, int uType, double uBad,
+                                               const void* d_v, int vType, double vBad, size_t nz,
+                                               void* d_uOut, void* d_vOut, void* stream, int* path);
 
 /* ------------------------------------------------------ 2-D fill processes */
 /*
