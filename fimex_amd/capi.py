@@ -81,6 +81,14 @@ class ExtractInfo(ctypes.Structure):
                 ("fastestRuns", ctypes.c_size_t), ("referenceOrderDiffers", ctypes.c_int)]
 
 
+class Packing(ctypes.Structure):
+    """fimex_amd_packing: how a variable is stored -- its CDM_* type code, _FillValue, scale_factor and add_offset."""
+    _fields_ = [("type", ctypes.c_int), ("fill", ctypes.c_double), ("scale", ctypes.c_double), ("offset", ctypes.c_double)]
+
+    def __init__(self, type, fill, scale=1.0, offset=0.0):
+        super().__init__(int(type), float(fill), float(scale), float(offset))
+
+
 class VerticalInfo(ctypes.Structure):
     _fields_ = [("nx", ctypes.c_size_t), ("ny", ctypes.c_size_t), ("nt", ctypes.c_size_t), ("nzi", ctypes.c_size_t), ("nzo", ctypes.c_size_t),
                 ("method", ctypes.c_int), ("entryBytes", ctypes.c_size_t)]
@@ -91,6 +99,7 @@ _D = ctypes.POINTER(ctypes.c_double)
 _Z = ctypes.c_size_t
 _ZP = ctypes.POINTER(ctypes.c_size_t)
 _V = ctypes.c_void_p
+_PK = ctypes.POINTER(Packing)
 
 # name -> (restype, argtypes); every symbol include/fimex_amd.h declares
 SYMBOLS = {
@@ -199,6 +208,10 @@ SYMBOLS = {
     "fimex_amd_merge_apply_device": (ctypes.c_int, [_V, _V, _V, _Z, _V, _V]),
     "fimex_amd_merge_apply_host": (ctypes.c_int, [_V, _F, _F, _Z, _F]),
     "fimex_amd_merge_apply_chain_device": (ctypes.c_int, [_V, _V, _V, _Z, _V, _V]),
+    "fimex_amd_border_smooth_typed_device": (ctypes.c_int, [_V, _PK, _V, _PK, _V, _Z, _Z, _Z, _Z, _Z, ctypes.c_int, _V]),
+    "fimex_amd_overlay_typed_device": (ctypes.c_int, [_V, _PK, _V, _PK, _V, _Z, _V]),
+    "fimex_amd_merge_apply_typed_device": (ctypes.c_int, [_V, _V, _PK, _V, _PK, _Z, _V, _V, ctypes.POINTER(ctypes.c_int)]),
+    "fimex_amd_merge_apply_typed_chain_device": (ctypes.c_int, [_V, _V, _PK, _V, _PK, _Z, _V, _V]),
     "fimex_amd_project_values_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z]),
     "fimex_amd_project_values_device": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _V, _V, _Z, _V]),
     "fimex_amd_project_axes_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z, _Z, _D, _D]),
@@ -255,6 +268,13 @@ VECTOR_REGRID_TYPED_HOST_SYMBOLS = {
                                                                 _V, _V, _Z, _ZP]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_merge_typed_host.h declares: grid merging on stored types, on host buffers
+MERGE_TYPED_HOST_SYMBOLS = {
+    "fimex_amd_border_smooth_typed_host": (ctypes.c_int, [_V, _PK, _V, _PK, _V, _Z, _Z, _Z, _Z, _Z, ctypes.c_int]),
+    "fimex_amd_overlay_typed_host": (ctypes.c_int, [_V, _PK, _V, _PK, _V, _Z]),
+    "fimex_amd_merge_apply_typed_host": (ctypes.c_int, [_V, _V, _PK, _V, _PK, _Z, _V]),
+}
+
 # name -> (restype, argtypes); every symbol include/fimex_amd_vertical_plan_host.h declares: the entries of (8f n5b) on host buffers
 VERTICAL_PLAN_HOST_SYMBOLS = {
     "fimex_amd_vertical_plan_create_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, ctypes.POINTER(VerticalLevelsStruct),
@@ -279,7 +299,7 @@ def _open(path):
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
             EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()) + list(VECTOR_REGRID_HOST_SYMBOLS.items()) + list(
-            VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()):
+            VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()) + list(MERGE_TYPED_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1218,6 +1238,49 @@ def overlay_device(d_top, d_base, d_out, n, stream=0):
     _check(load().fimex_amd_overlay_device(d_top, d_base, d_out, n, stream))
 
 
+def _typed(a, packing):
+    a = np.ascontiguousarray(a)
+    if cdm_type_of(a.dtype) != packing.type:
+        raise TypeError("the array's dtype %s is not the packing's type %d" % (a.dtype, packing.type))
+    return a
+
+
+def border_smooth_typed_host(inner, innerPacking, outerOnInner, outerPacking, transitionWidth=5, borderWidth=2, useOuterIfInnerUndefined=True):
+    """CDMBorderSmoothing::getDataSlice on two [nz][ny][nx] (or [ny][nx]) host arrays in their stored types, each with its Packing
+    -> the smoothed field in the inner's type and packing."""
+    i, o = _typed(inner, innerPacking), _typed(outerOnInner, outerPacking)
+    if i.shape != o.shape or i.ndim < 2:
+        raise ValueError("inner and outer differ in shape")
+    ny, nx = i.shape[-2:]
+    out = np.empty_like(i)
+    _check(load().fimex_amd_border_smooth_typed_host(i.ctypes.data, ctypes.byref(innerPacking), o.ctypes.data, ctypes.byref(outerPacking),
+                                                     out.ctypes.data, nx, ny, i.size // max(nx * ny, 1), transitionWidth, borderWidth,
+                                                     int(bool(useOuterIfInnerUndefined))))
+    return out
+
+
+def border_smooth_typed_device(d_inner, innerPacking, d_outerOnInner, outerPacking, d_out, nx, ny, nz, transitionWidth=5, borderWidth=2,
+                               useOuterIfInnerUndefined=True, stream=0):
+    """The same on device pointers; d_out may be d_inner, and d_outerOnInner where both types have one size."""
+    _check(load().fimex_amd_border_smooth_typed_device(d_inner, ctypes.byref(innerPacking), d_outerOnInner, ctypes.byref(outerPacking), d_out, nx,
+                                                       ny, nz, transitionWidth, borderWidth, int(bool(useOuterIfInnerUndefined)), stream))
+
+
+def overlay_typed_host(top, topPacking, base, basePacking):
+    """CDMOverlay::getDataSlice on two host arrays in their stored types -> the top's type and packing."""
+    t, b = _typed(top, topPacking), _typed(base, basePacking)
+    if t.shape != b.shape:
+        raise ValueError("top and base differ in shape")
+    out = np.empty_like(t)
+    _check(load().fimex_amd_overlay_typed_host(t.ctypes.data, ctypes.byref(topPacking), b.ctypes.data, ctypes.byref(basePacking), out.ctypes.data,
+                                               t.size))
+    return out
+
+
+def overlay_typed_device(d_top, topPacking, d_base, basePacking, d_out, n, stream=0):
+    _check(load().fimex_amd_overlay_typed_device(d_top, ctypes.byref(topPacking), d_base, ctypes.byref(basePacking), d_out, n, stream))
+
+
 class MergePlan:
     """fimex_amd_merge_plan: CDMMerger's data path on three backward RegridPlans (outer -> inner grid, inner -> target,
     outer -> target), which it keeps alive."""
@@ -1258,6 +1321,31 @@ class MergePlan:
     def apply_chain_device(self, d_inner, d_outer, nz, d_out, stream=0):
         """The same merge by the plain applies and the two elementwise kernels (cross-check and yardstick of the fused kernels)."""
         _check(load().fimex_amd_merge_apply_chain_device(self._h, d_inner, d_outer, nz, d_out, stream))
+
+    def apply_typed_device(self, d_inner, innerPacking, d_outer, outerPacking, nz, d_out, stream=0):
+        """The merge on variables in their stored types, each with its Packing; d_out holds the inner's type in the inner's packing.
+        Returns the path: 1 the two fused kernels, 0 the chain of apply_typed_chain_device."""
+        path = ctypes.c_int(-1)
+        _check(load().fimex_amd_merge_apply_typed_device(self._h, d_inner, ctypes.byref(innerPacking), d_outer, ctypes.byref(outerPacking), nz,
+                                                         d_out, stream, ctypes.byref(path)))
+        return path.value
+
+    def apply_typed_chain_device(self, d_inner, innerPacking, d_outer, outerPacking, nz, d_out, stream=0):
+        """The same by regrid_apply_typed_device three times and the two typed elementwise kernels (cross-check and yardstick)."""
+        _check(load().fimex_amd_merge_apply_typed_chain_device(self._h, d_inner, ctypes.byref(innerPacking), d_outer, ctypes.byref(outerPacking),
+                                                               nz, d_out, stream))
+
+    def apply_typed_host(self, inner, innerPacking, outer, outerPacking):
+        """The same on host arrays inner [nz][iy][ix] and outer [nz][oy][ox] in their stored types -> [nz][ty][tx] in the inner's."""
+        oi = self._plans[0]
+        i, o = _typed(inner, innerPacking).ravel(), _typed(outer, outerPacking).ravel()
+        nz = i.size // (oi.outX * oi.outY)
+        if i.size != nz * oi.outX * oi.outY or o.size != nz * oi.inX * oi.inY:
+            raise ValueError("inner and outer do not hold the same number of whole slices")
+        out = np.empty((nz, self.outY, self.outX), dtype=i.dtype)
+        _check(load().fimex_amd_merge_apply_typed_host(self._h, i.ctypes.data, ctypes.byref(innerPacking), o.ctypes.data, ctypes.byref(outerPacking),
+                                                       nz, out.ctypes.data))
+        return out
 
 
 def project_values_host(proj_input, proj_output, x, y):

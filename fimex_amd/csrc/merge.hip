@@ -10,8 +10,11 @@
 // A lane owns one cell of a kTileX x kTileY tile and keeps its class (smoothing) or its plan entries (regrid) in registers over the
 // z loop; kAhead slices are in flight per lane.  Every slice has its own buffer descriptor, so a batch of any length is addressed
 // with 32-bit lane offsets (a slice holds fewer than 2^30 cells, plan.hpp).  The plan entries and the stencil arithmetic are those
-// of stencil_math.hpp.  Built with -ffp-contract=off: I + alpha * diff is a multiply and an add, as in the reference.
+// of stencil_math.hpp, the cell classes and the blend those of merge_math.hpp.  Built with -ffp-contract=off: I + alpha * diff is a
+// multiply and an add, as in the reference.
 #include "gather_entry.hpp"
+#include "merge_launch.hpp"
+#include "merge_math.hpp"
 #include "plan.hpp"
 
 #include <cmath>
@@ -20,69 +23,20 @@ namespace fimex_amd {
 
 namespace {
 
-constexpr int kTileX = 64, kTileY = 4;  // a wave per row
-static_assert(kTileX * kTileY == kBlock, "a tile is one workgroup");
-constexpr int kAhead = 4;               // slices whose loads are in flight together
+using merge_launch::kAhead;
+using merge_launch::kTileX;
+using merge_launch::kTileY;
+using merge_launch::stencil_of;
+using merge_launch::tile_grid;
 
-// ---- CDMBorderSmoothing_Linear::operator() (:41-85), split into what depends on the cell and what depends on the values.
-// size_t arithmetic that wraps, as the reference's: xmax2 = nx - bw and xmin2 = xmax2 - tw may wrap, and the comparisons decide
-// the branch on the wrapped values.
-enum : int { kOuter = 0, kInner = 1, kBlend = 2 };
-struct SmoothClass {
-    int kind;
-    double alpha;  // kBlend: divided by the transition width and clamped (:79-83)
-};
+// CDMBorderSmoothing_Linear::operator() on float interpolation arrays: the cell classes and the blend of merge_math.hpp
+using merge_math::SmoothClass;
+using merge_math::smooth_class;
 
-__device__ __forceinline__ double dist(double dx, double dy) { return sqrt(dx * dx + dy * dy); }  // :33-35
-
-__device__ __forceinline__ SmoothClass smooth_class(uint64_t x, uint64_t y, uint64_t nx, uint64_t ny, uint64_t tw, uint64_t bw)
-{
-    const uint64_t xmin1 = bw, xmax1 = xmin1 + tw;      // :46
-    const uint64_t ymin1 = bw, ymax1 = ymin1 + tw;      // :47
-    const uint64_t xmax2 = nx - bw, xmin2 = xmax2 - tw;  // :48
-    const uint64_t ymax2 = ny - bw, ymin2 = ymax2 - tw;  // :49
-    SmoothClass c{kOuter, 0.};
-    if (x < xmin1 || x >= xmax2 || y < ymin1 || y >= ymax2) return c;  // :52
-    c.kind = kInner;
-    if (x >= xmax1 && x < xmin2 && y >= ymax1 && y < ymin2) return c;  // :54
-    c.kind = kBlend;
-    double alpha = 0;
-    if (x < xmax1) {  // :60-78
-        if (y < ymax1) alpha = dist((double)(xmax1 - x), (double)(ymax1 - y));
-        else if (y >= ymin2) alpha = dist((double)(xmax1 - x), (double)(y - ymin2));
-        else alpha = (double)(xmax1 - x);
-    } else if (x >= xmin2) {
-        if (y < ymax1) alpha = dist((double)(x - xmin2), (double)(ymax1 - y));
-        else if (y >= ymin2) alpha = dist((double)(x - xmin2), (double)(y - ymin2));
-        else alpha = (double)(x - xmin2);
-    } else if (y < ymax1) {
-        alpha = (double)(ymax1 - y);
-    } else if (y >= ymin2) {
-        alpha = (double)(y - ymin2);
-    }
-    alpha /= (double)tw;
-    if (alpha > 1) alpha = 1;
-    else if (alpha < 0) alpha = 0;
-    c.alpha = alpha;
-    return c;
-}
-
-// true: smooth_value reads the outer value for this inner value
-__device__ __forceinline__ bool needs_outer(const SmoothClass& c, float inner, bool useOuter)
-{
-    return inner != inner ? useOuter : c.kind != kInner;
-}
-
-// CDMBorderSmoothing.cc:129-139 on one cell; outer is read only where needs_outer says so
+__device__ __forceinline__ bool needs_outer(const SmoothClass& c, float inner, bool useOuter) { return merge_math::needs_outer<float>(c, inner, useOuter); }
 __device__ __forceinline__ float smooth_value(const SmoothClass& c, float inner, float outer, bool useOuter)
 {
-    if (inner != inner) return useOuter ? outer : undefined_f();  // :132-133
-    if (c.kind == kInner || outer != outer) return inner;         // :134-135, Linear :54-55
-    if (c.kind == kOuter) return outer;                           // Linear :52-53
-    const double valueI = (double)inner, valueO = (double)outer;
-    const double diff = valueO - valueI;  // :56
-    if (diff == 0) return outer;          // :57-58
-    return (float)(valueI + c.alpha * diff);
+    return merge_math::smooth_value<float>(c, inner, outer, useOuter);
 }
 
 struct SmoothArgs {
@@ -235,34 +189,6 @@ __global__ void __launch_bounds__(kBlock) merge_overlay_kernel(const MergeOverla
         float v = es.value(make_rsrc(a.s + (size_t)z * a.st.inLayer, a.st.inBytes));
         if (v != v) v = eo.value(make_rsrc(a.outer + (size_t)z * a.ot.inLayer, a.ot.inBytes));
         st_stream(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, 0, v);
-    }
-}
-
-// tiles of one slice in x and y, chunks of slices in z: enough workgroups to fill the device, chunks long enough to amortise the
-// per-cell set-up (class, plan entries)
-dim3 tile_grid(size_t nx, size_t ny, size_t nz, uint32_t& zPerBlock)
-{
-    FA_REQUIRE(nx * ny <= kMaxSliceCells, "a slice must have fewer than 2^30 cells");
-    FA_REQUIRE(nz <= 0xFFFFFFFFu, "too many slices");
-    const size_t tilesX = ceil_div(nx, kTileX), tilesY = ceil_div(ny, kTileY);
-    FA_REQUIRE(tilesY <= 65535, "grid too tall for one launch");
-    const size_t wantBlocks = 256 * 8 * 4;
-    size_t chunks = ceil_div(wantBlocks, tilesX * tilesY);
-    if (chunks > nz) chunks = nz;
-    size_t zpb = ceil_div(nz, chunks);
-    zpb = ceil_div(zpb, kAhead) * kAhead;
-    if (ceil_div(nz, zpb) > 65535) zpb = ceil_div(nz, (size_t)65535);
-    zPerBlock = (uint32_t)zpb;
-    return dim3((uint32_t)tilesX, (uint32_t)tilesY, (uint32_t)ceil_div(nz, zpb));
-}
-
-int stencil_of(const fimex_amd_regrid_plan& p)
-{
-    switch (p.kind) {
-    case PlanKind::Nearest: return 1;
-    case PlanKind::Bilinear: return 2;
-    case PlanKind::Bicubic: return 4;
-    default: throw Error("merge: not a backward plan");
     }
 }
 

@@ -296,6 +296,17 @@ void launch_overlay(const float* d_top, const float* d_base, float* d_out, size_
 void launch_merge_fused(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream);
 void launch_merge_chain(const fimex_amd_merge_plan& m, const float* d_inner, const float* d_outer, size_t nz, float* d_out, hipStream_t stream);
 
+// merge_typed.hip: the same on variables in their stored types, each with its own packing; the result has the inner's.
+// launch_merge_typed_fused returns false, with nothing launched, where the fused kernels do not serve the call
+void launch_border_smooth_typed(const void* d_inner, const fimex_amd_packing& pi, const void* d_outerOnInner, const fimex_amd_packing& po, void* d_out,
+                                size_t nx, size_t ny, size_t nz, size_t transitionWidth, size_t borderWidth, bool useOuter, hipStream_t stream);
+void launch_overlay_typed(const void* d_top, const fimex_amd_packing& pt, const void* d_base, const fimex_amd_packing& pb, void* d_out, size_t n,
+                          hipStream_t stream);
+bool launch_merge_typed_fused(const fimex_amd_merge_plan& m, const void* d_inner, const fimex_amd_packing& pi, const void* d_outer,
+                              const fimex_amd_packing& po, size_t nz, void* d_out, hipStream_t stream);
+void launch_merge_typed_chain(const fimex_amd_merge_plan& m, const void* d_inner, const fimex_amd_packing& pi, const void* d_outer,
+                              const fimex_amd_packing& po, size_t nz, void* d_out, hipStream_t stream);
+
 // projection.hip: pj_transform-level plan building on the device (strings: projection_parse.hip, point math: proj_math.hpp)
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);
 void launch_project_axes(const char* projIn, const char* projOut, const double* h_xAxis, const double* h_yAxis, size_t ix, size_t iy,

@@ -8,6 +8,7 @@
 // go one by one.  Where no such start exists (pointers whose misalignments differ) head = n and everything goes one by one.  A lane
 // reads all of a group before it writes any of it and groups are disjoint, so out may be in itself when the sizes agree.  No LDS,
 // no scratch; the grid is capped and strides.
+#include "merge_math.hpp"
 #include "plan.hpp"
 #include "typed_convert.hpp"
 
@@ -25,21 +26,11 @@ struct alignas(16) Group {
     T v[N];
 };
 
+// Utils.h:443-464, stated once in merge_math.hpp for the conversions and the merge on stored types.  A derived struct of this
+// file's own and not a using-declaration on purpose: the kernels below take it by value, so its name is part of their mangled
+// symbols, and those stay what they were before the arithmetic moved (the device assembly is unchanged but for the id symbol).
 template <typename IN, typename OUT>
-struct ScaleValue {
-    IN oldFill;
-    bool hasFill;  // false: (IN)oldFill does not exist, nothing compares equal to it
-    double a, b;   // oldScale / newScale, (oldOffset - newOffset) / newScale
-    OUT newFill;
-    // Utils.h:456-460: in double, then data_caster<OUT, double>: mifi_round for an integer OUT, a plain cast otherwise
-    __device__ __forceinline__ OUT operator()(IN in) const
-    {
-        if ((hasFill && in == oldFill) || (std::is_floating_point<IN>::value && in != in)) return newFill;
-        const double d = a * (double)in + b;
-        if (std::is_integral<OUT>::value) return (OUT)mifi_round(d);
-        return (OUT)d;
-    }
-};
+struct ScaleValue : merge_math::ScaleValue<IN, OUT> {};
 
 template <typename IN, typename OUT>
 __global__ void __launch_bounds__(kBlock) scaled_kernel(const IN* in, OUT* out, size_t n, size_t head, const ScaleValue<IN, OUT> sv)
@@ -63,16 +54,7 @@ __global__ void __launch_bounds__(kBlock) scaled_kernel(const IN* in, OUT* out, 
     }
 }
 
-// static_cast<T>(v) of a double is defined: trunc(v) lies in the range of an integer T, a finite v within that of float
-template <typename T>
-bool representable(double v)
-{
-    if (std::is_same<T, float>::value) return !std::isfinite(v) || std::fabs(v) <= (double)std::numeric_limits<float>::max();
-    if (std::is_floating_point<T>::value) return true;
-    if (v != v) return false;
-    const double t = std::trunc(v);
-    return t >= (double)std::numeric_limits<T>::min() && t < std::ldexp(1.0, std::numeric_limits<T>::digits);
-}
+using merge_math::representable;
 
 // elements in front of the first group, or n where the two pointers never reach a 16-byte boundary together
 template <typename IN, typename OUT>

@@ -18,6 +18,9 @@ __device__ __forceinline__ float as_float_nan(T v, float bad, bool hasBad)
     return (hasBad && f == bad) ? undefined_f() : f;
 }
 
+// merge_math.hpp holds twins of the two functions below that also compile for the host (mifi_round_d, round_to_stored); the typed
+// merge chain runs these, its fused kernels run the twins, and tests/test_gpu_merge_typed.py compares the two byte for byte.  A
+// change to either belongs in both.
 // MetNoFimex::round(double) (include/fimex/Utils.h:72-75): lround, then long -> int.  Outside the range of long the
 // reference is unspecified; LONG_MIN (what glibc/x86-64 yields) is kept (DESIGN.md divergence D6).
 __device__ __forceinline__ int mifi_round(double num)

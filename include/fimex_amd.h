@@ -655,9 +655,9 @@ int fimex_amd_omega_to_vertical_wind_host(const fimex_amd_vertical_levels* press
  *   4  out = isnan(ST) ? OT : ST                      (CDMOverlay::getDataSlice)
  * Every step is the reference's arithmetic operation by operation; the results are the reference's bit for bit for variables
  * stored as float with scale 1 and offset 0 (a double variable is narrowed to float before the blend of step 2 here, after it in
- * the reference).  Packed variables (the reference rounds them to the stored type after
- * steps 1, 2 and 3) and vector pairs (the interpolators rotate them) go step by step through the elementwise entries below,
- * fimex_amd_regrid_apply_typed_device and the rotation entries. */
+ * the reference).  Packed variables, and every variable in its stored type, take the *_typed entries at the end of this block.
+ * Vector pairs (the interpolators rotate them) go step by step through the elementwise entries below and the rotation entries
+ * (INTEGRATION.md). */
 /**
  * CDMBorderSmoothing::getDataSlice (src/CDMBorderSmoothing.cc:129-139) with CDMBorderSmoothing_Linear::operator()
  * (src/CDMBorderSmoothing_Linear.cc:41-85) on [nz][ny][nx] slices: an undefined inner value gives the outer one
@@ -699,6 +699,52 @@ int fimex_amd_merge_apply_host(const fimex_amd_merge_plan* plan, const float* in
  *  and the yardstick of the fused kernels (as fimex_amd_regrid_apply_gather_device is for the staged ones). */
 int fimex_amd_merge_apply_chain_device(const fimex_amd_merge_plan* plan, const float* d_inner, const float* d_outer, size_t nz, float* d_out,
                                        void* stream);
+
+/* Grid merging on variables in their stored types: what CDMBorderSmoothing::getDataSlice and
+ * CDMOverlay::getDataSlice compute on packed variables.  Both fields are read through getScaledDataSlice, each with its own
+ * scale_factor, add_offset and _FillValue (ScaleValue to double, the fill value as NaN), blended in double, and packed by
+ * convertDataType with the packing of the inner (top) variable, whose type the result has.  The three regrids are
+ * fimex_amd_regrid_apply_typed_device on the raw counts:
+ *   1  OI  = regridT(outer -> inner grid)                               in the outer's type
+ *   2  S   = pack(smooth(unpack(inner), unpack(OI)))                    in the inner's type and packing
+ *   3  ST  = regridT(S -> target), OT = regridT(outer -> target)
+ *   4  out = pack(isnan(unpack(ST)) ? unpack(OT) : unpack(ST))          a defined value is unpacked and packed again
+ * unpack and pack are what fimex_amd_convert_scaled_device computes (integer results through mifi_round and the wrapping casts,
+ * not clamped; a fill value that does not exist in the input type matches nothing).  The host forms are declared in
+ * fimex_amd_merge_typed_host.h. */
+typedef struct fimex_amd_packing {
+    int type;      /* fimex_amd_datatype, one of the ten numeric types */
+    double fill;   /* _FillValue */
+    double scale;  /* scale_factor */
+    double offset; /* add_offset */
+} fimex_amd_packing;
+/**
+ * fimex_amd_border_smooth_device on [nz][ny][nx] slices of innerPacking->type and outerPacking->type; d_out holds the inner's type in
+ * the inner's packing.  d_out may be d_inner, and may be d_outerOnInner where the two element sizes agree; any other overlap is
+ * refused, as are a NULL packing, a type without element size (NAT, STRING) and an inner fill value that is not representable in
+ * the inner's type (fimex_amd_convert_scaled_device's rule).
+ */
+int fimex_amd_border_smooth_typed_device(const void* d_inner, const fimex_amd_packing* innerPacking, const void* d_outerOnInner,
+                                         const fimex_amd_packing* outerPacking, void* d_out, size_t nx, size_t ny, size_t nz,
+                                         size_t transitionWidth, size_t borderWidth, int useOuterIfInnerUndefined, void* stream);
+/** fimex_amd_overlay_device on n values of topPacking->type and basePacking->type; d_out holds the top's type in the top's
+ *  packing.  The same aliasing rule and refusals. */
+int fimex_amd_overlay_typed_device(const void* d_top, const fimex_amd_packing* topPacking, const void* d_base,
+                                   const fimex_amd_packing* basePacking, void* d_out, size_t n, void* stream);
+/**
+ * Steps 1-4 on d_inner [nz][iy][ix] of innerPacking->type and d_outer [nz][oy][ox] of outerPacking->type -> d_out [nz][ty][tx] of the
+ * inner's type in the inner's packing.  *path (may be NULL; written as 0 before any check): 1 the two fused kernels ran (both
+ * variables short, or both unsigned short, and the three buffers aligned to their element), 0 the chain below ran inside the
+ * entry.  Same results either way.  d_out must not overlap the inputs; nz == 0 does nothing.  Runs on the plans' device.
+ */
+int fimex_amd_merge_apply_typed_device(const fimex_amd_merge_plan* plan, const void* d_inner, const fimex_amd_packing* innerPacking,
+                                       const void* d_outer, const fimex_amd_packing* outerPacking, size_t nz, void* d_out, void* stream,
+                                       int* path);
+/** The same result as five launches on stream-ordered temporaries of the stored types: regridT three times and the two typed
+ *  elementwise kernels.  The cross-check and the yardstick of the fused kernels. */
+int fimex_amd_merge_apply_typed_chain_device(const fimex_amd_merge_plan* plan, const void* d_inner, const fimex_amd_packing* innerPacking,
+                                             const void* d_outer, const fimex_amd_packing* outerPacking, size_t nz, void* d_out,
+                                             void* stream);
 
 /* ------------- scaled reads and writes, theta2T, humidity, accumulate (8f n9) */
 /* The arithmetic around the entries above that the reference keeps in its readers and decorators: unpacking stored data
