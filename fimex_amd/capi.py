@@ -212,6 +212,8 @@ SYMBOLS = {
     "fimex_amd_overlay_typed_device": (ctypes.c_int, [_V, _PK, _V, _PK, _V, _Z, _V]),
     "fimex_amd_merge_apply_typed_device": (ctypes.c_int, [_V, _V, _PK, _V, _PK, _Z, _V, _V, ctypes.POINTER(ctypes.c_int)]),
     "fimex_amd_merge_apply_typed_chain_device": (ctypes.c_int, [_V, _V, _PK, _V, _PK, _Z, _V, _V]),
+    "fimex_amd_merge_apply_vector_device": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _V, _V]),
+    "fimex_amd_merge_apply_vector_chain_device": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _V, _V]),
     "fimex_amd_project_values_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z]),
     "fimex_amd_project_values_device": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _V, _V, _Z, _V]),
     "fimex_amd_project_axes_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z, _Z, _D, _D]),
@@ -275,6 +277,11 @@ MERGE_TYPED_HOST_SYMBOLS = {
     "fimex_amd_merge_apply_typed_host": (ctypes.c_int, [_V, _V, _PK, _V, _PK, _Z, _V]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_merge_vector_host.h declares: the merge of an x/y vector pair on host buffers
+MERGE_VECTOR_HOST_SYMBOLS = {
+    "fimex_amd_merge_apply_vector_host": (ctypes.c_int, [_V, _V, _V, _V, _F, _F, _F, _F, _Z, _F, _F]),
+}
+
 # name -> (restype, argtypes); every symbol include/fimex_amd_vertical_plan_host.h declares: the entries of (8f n5b) on host buffers
 VERTICAL_PLAN_HOST_SYMBOLS = {
     "fimex_amd_vertical_plan_create_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, ctypes.POINTER(VerticalLevelsStruct),
@@ -299,7 +306,7 @@ def _open(path):
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
             EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()) + list(VECTOR_REGRID_HOST_SYMBOLS.items()) + list(
-            VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()) + list(MERGE_TYPED_HOST_SYMBOLS.items()):
+            VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()) + list(MERGE_TYPED_HOST_SYMBOLS.items()) + list(MERGE_VECTOR_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1346,6 +1353,32 @@ class MergePlan:
         _check(load().fimex_amd_merge_apply_typed_host(self._h, i.ctypes.data, ctypes.byref(innerPacking), o.ctypes.data, ctypes.byref(outerPacking),
                                                        nz, out.ctypes.data))
         return out
+
+    def apply_vector_device(self, outerToInnerVec, innerToTargetVec, outerToTargetVec, d_innerU, d_innerV, d_outerU, d_outerV, nz, d_outU, d_outV,
+                            stream=0):
+        """The merge of an x/y vector pair of float arrays: each of the three regrids is followed by the rotation of its VectorPlan
+        (outerToInnerVec on the inner grid, the other two on the target).  Two fused kernels."""
+        _check(load().fimex_amd_merge_apply_vector_device(self._h, outerToInnerVec._h, innerToTargetVec._h, outerToTargetVec._h, d_innerU, d_innerV,
+                                                          d_outerU, d_outerV, nz, d_outU, d_outV, stream))
+
+    def apply_vector_chain_device(self, outerToInnerVec, innerToTargetVec, outerToTargetVec, d_innerU, d_innerV, d_outerU, d_outerV, nz, d_outU,
+                                  d_outV, stream=0):
+        """The same step by step: the pair regridded and rotated three times, the smoothing and the overlay once per component
+        (cross-check and yardstick of the fused kernels)."""
+        _check(load().fimex_amd_merge_apply_vector_chain_device(self._h, outerToInnerVec._h, innerToTargetVec._h, outerToTargetVec._h, d_innerU,
+                                                                d_innerV, d_outerU, d_outerV, nz, d_outU, d_outV, stream))
+
+    def apply_vector_host(self, outerToInnerVec, innerToTargetVec, outerToTargetVec, innerU, innerV, outerU, outerV):
+        """The same on float32 host arrays: inner [nz][iy][ix] and outer [nz][oy][ox] components -> (outU, outV), each [nz][ty][tx]."""
+        oi = self._plans[0]
+        iu, iv, ou, ov = (_f32(a).ravel() for a in (innerU, innerV, outerU, outerV))
+        nz = iu.size // (oi.outX * oi.outY)
+        if iu.size != nz * oi.outX * oi.outY or iv.size != iu.size or ou.size != nz * oi.inX * oi.inY or ov.size != ou.size:
+            raise ValueError("the four components do not hold the same number of whole slices")
+        outU, outV = (np.empty((nz, self.outY, self.outX), dtype=np.float32) for _ in range(2))
+        _check(load().fimex_amd_merge_apply_vector_host(self._h, outerToInnerVec._h, innerToTargetVec._h, outerToTargetVec._h, _fp(iu), _fp(iv),
+                                                        _fp(ou), _fp(ov), nz, _fp(outU), _fp(outV)))
+        return outU, outV
 
 
 def project_values_host(proj_input, proj_output, x, y):

@@ -13,6 +13,25 @@
 
 using namespace fimex_amd;
 
+namespace fimex_amd {
+
+// CDMInterpolator.cc:259-277 on device buffers: the fused kernel where it serves the plan and the batch, else the chain it
+// replaces, launch for launch; returns the path taken (declared in plan.hpp: the chain of merge_vector.hip runs it too)
+int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
+                      float* d_uOut, float* d_vOut, hipStream_t stream)
+{
+    if (staged2_vector_serves(plan, nz)) {
+        launch_staged2_apply_vector(plan, vec, d_u, d_v, nz, d_uOut, d_vOut, stream);
+        return 1;
+    }
+    apply_plan_device(plan, d_u, nz, d_uOut, stream);
+    apply_plan_device(plan, d_v, nz, d_vOut, stream);
+    launch_vector_values(vec, d_uOut, d_vOut, nz, stream);
+    return 0;
+}
+
+}  // namespace fimex_amd
+
 namespace {
 
 template <class Call>
@@ -83,21 +102,6 @@ void check_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector
                        const float* uOut, const float* vOut)
 {
     check_vector_pair_sized(plan, vec, u, sizeof(float), v, sizeof(float), nz, uOut, vOut);
-}
-
-// CDMInterpolator.cc:259-277 on device buffers: the fused kernel where it serves the plan and the batch, else the chain it
-// replaces, launch for launch; returns the path taken
-int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
-                      float* d_uOut, float* d_vOut, hipStream_t stream)
-{
-    if (staged2_vector_serves(plan, nz)) {
-        launch_staged2_apply_vector(plan, vec, d_u, d_v, nz, d_uOut, d_vOut, stream);
-        return 1;
-    }
-    apply_plan_device(plan, d_u, nz, d_uOut, stream);
-    apply_plan_device(plan, d_v, nz, d_vOut, stream);
-    launch_vector_values(vec, d_uOut, d_vOut, nz, stream);
-    return 0;
 }
 
 // CDMInterpolator.cc:251-285 on device buffers in the components' stored types: the kernel on the stored type (path 2) where it

@@ -23,9 +23,12 @@ namespace fimex_amd {
 
 namespace {
 
+using merge_launch::FloatScratch;
 using merge_launch::kAhead;
 using merge_launch::kTileX;
 using merge_launch::kTileY;
+using merge_launch::plan_ref;
+using merge_launch::PlanRef;
 using merge_launch::stencil_of;
 using merge_launch::tile_grid;
 
@@ -91,25 +94,6 @@ __global__ void __launch_bounds__(kBlock) overlay_kernel(const float* top, const
         if (i < n) out[i] = t[k] != t[k] ? b[k] : t[k];
     }
 }
-
-// ---- a backward plan's arrays; an entry is decoded once per cell and evaluated slice by slice (gather_entry.hpp: an undefined
-// entry issues loads that are dropped and gives NaN, so the lane stays on the common path)
-struct PlanRef {
-    const uint32_t* pos;
-    const float *xf, *yf;
-    const double *xfd, *yfd;
-    uint32_t ix;       // source row length
-    uint32_t inBytes;  // bytes of a source slice
-    size_t inLayer;    // cells of a source slice
-
-    template <int STENCIL>
-    __device__ __forceinline__ GatherEntry<STENCIL, float> entry(uint32_t cell) const
-    {
-        if constexpr (STENCIL == 4) return {pos[cell], xfd[cell], yfd[cell], ix};
-        else if constexpr (STENCIL == 2) return {pos[cell], xf[cell], yf[cell], ix};
-        else return {pos[cell], 0.f, 0.f, ix};
-    }
-};
 
 struct MergeSmoothArgs {
     PlanRef oi;           // outer -> inner grid
@@ -192,20 +176,6 @@ __global__ void __launch_bounds__(kBlock) merge_overlay_kernel(const MergeOverla
     }
 }
 
-PlanRef plan_ref(const fimex_amd_regrid_plan& p)
-{
-    PlanRef r{};
-    r.pos = p.pos.get();
-    r.xf = p.xf.get();
-    r.yf = p.yf.get();
-    r.xfd = p.xfd.get();
-    r.yfd = p.yfd.get();
-    r.ix = (uint32_t)p.inX;
-    r.inLayer = p.inX * p.inY;
-    r.inBytes = (uint32_t)(r.inLayer * 4);
-    return r;
-}
-
 template <int ST>
 void launch_overlay_st(int ot, dim3 grid, const MergeOverlayArgs& a, hipStream_t stream)
 {
@@ -214,23 +184,6 @@ void launch_overlay_st(int ot, dim3 grid, const MergeOverlayArgs& a, hipStream_t
     else if (ot == 2) merge_overlay_kernel<ST, 2><<<grid, block, 0, stream>>>(a);
     else merge_overlay_kernel<ST, 4><<<grid, block, 0, stream>>>(a);
 }
-
-// stream-ordered float scratch of one call, freed on the stream behind the kernels that use it
-class FloatScratch {
-public:
-    FloatScratch(size_t floats, hipStream_t stream) : stream_(stream)
-    {
-        if (floats) FA_HIP(hipMallocAsync(reinterpret_cast<void**>(&p_), floats * sizeof(float), stream));
-    }
-    ~FloatScratch() { if (p_) (void)hipFreeAsync(p_, stream_); }
-    FloatScratch(const FloatScratch&) = delete;
-    FloatScratch& operator=(const FloatScratch&) = delete;
-    float* get() const { return p_; }
-
-private:
-    float* p_ = nullptr;
-    hipStream_t stream_;
-};
 
 }  // namespace
 

@@ -1,7 +1,9 @@
-// Launch geometry shared by the merge kernels on float arrays (merge.hip) and on stored types (merge_typed.hip): the tile of a
-// workgroup, the slices in flight per lane, the grid over tiles and chunks of slices, and the stencil size of a backward plan.
+// Launch geometry shared by the merge kernels on float arrays (merge.hip), on stored types (merge_typed.hip) and on float vector
+// pairs (merge_vector.hip): the tile of a workgroup, the slices in flight per lane, the grid over tiles and chunks of slices, the
+// stencil size of a backward plan, and for the two float files a plan's arrays as kernel arguments and the call's scratch.
 #pragma once
 
+#include "gather_entry.hpp"
 #include "plan.hpp"
 
 namespace fimex_amd {
@@ -38,6 +40,56 @@ inline int stencil_of(const fimex_amd_regrid_plan& p)
     default: throw Error("merge: not a backward plan");
     }
 }
+
+// ---- a backward plan's arrays on float slices; an entry is decoded once per cell and evaluated slice by slice (gather_entry.hpp:
+// an undefined entry issues loads that are dropped and gives NaN, so the lane stays on the common path)
+struct PlanRef {
+    const uint32_t* pos;
+    const float *xf, *yf;
+    const double *xfd, *yfd;
+    uint32_t ix;       // source row length
+    uint32_t inBytes;  // bytes of a source slice
+    size_t inLayer;    // cells of a source slice
+
+    template <int STENCIL>
+    __device__ __forceinline__ GatherEntry<STENCIL, float> entry(uint32_t cell) const
+    {
+        if constexpr (STENCIL == 4) return {pos[cell], xfd[cell], yfd[cell], ix};
+        else if constexpr (STENCIL == 2) return {pos[cell], xf[cell], yf[cell], ix};
+        else return {pos[cell], 0.f, 0.f, ix};
+    }
+};
+
+inline PlanRef plan_ref(const fimex_amd_regrid_plan& p)
+{
+    PlanRef r{};
+    r.pos = p.pos.get();
+    r.xf = p.xf.get();
+    r.yf = p.yf.get();
+    r.xfd = p.xfd.get();
+    r.yfd = p.yfd.get();
+    r.ix = (uint32_t)p.inX;
+    r.inLayer = p.inX * p.inY;
+    r.inBytes = (uint32_t)(r.inLayer * 4);
+    return r;
+}
+
+// stream-ordered float scratch of one call, freed on the stream behind the kernels that use it
+class FloatScratch {
+public:
+    FloatScratch(size_t floats, hipStream_t stream) : stream_(stream)
+    {
+        if (floats) FA_HIP(hipMallocAsync(reinterpret_cast<void**>(&p_), floats * sizeof(float), stream));
+    }
+    ~FloatScratch() { if (p_) (void)hipFreeAsync(p_, stream_); }
+    FloatScratch(const FloatScratch&) = delete;
+    FloatScratch& operator=(const FloatScratch&) = delete;
+    float* get() const { return p_; }
+
+private:
+    float* p_ = nullptr;
+    hipStream_t stream_;
+};
 
 }  // namespace merge_launch
 }  // namespace fimex_amd

@@ -307,6 +307,14 @@ bool launch_merge_typed_fused(const fimex_amd_merge_plan& m, const void* d_inner
 void launch_merge_typed_chain(const fimex_amd_merge_plan& m, const void* d_inner, const fimex_amd_packing& pi, const void* d_outer,
                               const fimex_amd_packing& po, size_t nz, void* d_out, hipStream_t stream);
 
+// merge_vector.hip: the same on an x/y vector pair of float arrays, rotated behind each of the three regrids
+void launch_merge_vector_fused(const fimex_amd_merge_plan& m, const fimex_amd_vector_plan& rotOI, const fimex_amd_vector_plan& rotST,
+                               const fimex_amd_vector_plan& rotOT, const float* d_innerU, const float* d_innerV, const float* d_outerU,
+                               const float* d_outerV, size_t nz, float* d_outU, float* d_outV, hipStream_t stream);
+void launch_merge_vector_chain(const fimex_amd_merge_plan& m, const fimex_amd_vector_plan& rotOI, const fimex_amd_vector_plan& rotST,
+                               const fimex_amd_vector_plan& rotOT, const float* d_innerU, const float* d_innerV, const float* d_outerU,
+                               const float* d_outerV, size_t nz, float* d_outU, float* d_outV, hipStream_t stream);
+
 // projection.hip: pj_transform-level plan building on the device (strings: projection_parse.hip, point math: proj_math.hpp)
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);
 void launch_project_axes(const char* projIn, const char* projOut, const double* h_xAxis, const double* h_yAxis, size_t ix, size_t iy,
@@ -341,6 +349,9 @@ fimex_amd_batch* batch_alloc_source(const fimex_amd_regrid_plan& plan, size_t nz
 void batch_free(fimex_amd_batch* batch);
 const fimex_amd_batch_info& batch_info(const fimex_amd_batch& batch);
 void apply_plan_device(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+// capi_vector.hip: a vector pair regridded and rotated as fimex_amd_regrid_apply_vector_device serves it; returns the path taken
+int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
+                      float* d_uOut, float* d_vOut, hipStream_t stream);
 
 // hostpipe.hip: streamed transfers for the *_host entry points
 using SliceChunkFn = std::function<void(const void* dRawIn, void* dRawOut, float* dFIn, float* dFOut, size_t nzc, hipStream_t stream)>;

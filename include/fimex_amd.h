@@ -656,8 +656,8 @@ int fimex_amd_omega_to_vertical_wind_host(const fimex_amd_vertical_levels* press
  * Every step is the reference's arithmetic operation by operation; the results are the reference's bit for bit for variables
  * stored as float with scale 1 and offset 0 (a double variable is narrowed to float before the blend of step 2 here, after it in
  * the reference).  Packed variables, and every variable in its stored type, take the *_typed entries at the end of this block.
- * Vector pairs (the interpolators rotate them) go step by step through the elementwise entries below and the rotation entries
- * (INTEGRATION.md). */
+ * An x/y vector pair, which every interpolator of the merger rotates behind its regrid, takes fimex_amd_merge_apply_vector_device
+ * behind the typed entries; packed pairs go step by step through the typed entries. */
 /**
  * CDMBorderSmoothing::getDataSlice (src/CDMBorderSmoothing.cc:129-139) with CDMBorderSmoothing_Linear::operator()
  * (src/CDMBorderSmoothing_Linear.cc:41-85) on [nz][ny][nx] slices: an undefined inner value gives the outer one
@@ -745,6 +745,35 @@ int fimex_amd_merge_apply_typed_device(const fimex_amd_merge_plan* plan, const v
 int fimex_amd_merge_apply_typed_chain_device(const fimex_amd_merge_plan* plan, const void* d_inner, const fimex_amd_packing* innerPacking,
                                              const void* d_outer, const fimex_amd_packing* outerPacking, size_t nz, void* d_out,
                                              void* stream);
+
+/**
+ * CDMMerger::getDataSlice on an x/y vector pair of float interpolation arrays, such as x_wind / y_wind.  Each of
+ * the merger's three CDMInterpolators rotates the pair behind its regrid (src/CDMInterpolator.cc:259-283) with the matrices of
+ * its CachedVectorReprojection: outerToInnerVec (R_oi) on the inner grid, innerToTargetVec (R_st) and outerToTargetVec (R_ot) on
+ * the target.  rot(R; u, v) is fimex_amd_vector_reproject_values_device on one cell:
+ *   1  (OIu, OIv) = rot(R_oi; regrid(outerU -> inner grid), regrid(outerV -> inner grid))
+ *   2  Su = smooth(innerU, OIu), Sv = smooth(innerV, OIv)                      component by component
+ *   3  (STu, STv) = rot(R_st; regrid(Su -> target), regrid(Sv -> target)),  (OTu, OTv) = rot(R_ot; regrid(outerU), regrid(outerV))
+ *   4  outU = isnan(STu) ? OTu : STu, outV = isnan(STv) ? OTv : STv            component by component
+ * A NaN in either regridded component, or in a cell's matrix, makes both rotated components NaN, so the next step falls back to
+ * the inner value (step 2) or the outer pair (step 4).  Two fused kernels, a lane per cell, every plan entry decoded once for both
+ * components; the smoothed pair is one stream-ordered scratch of 2 * nz * ix * iy floats.  The result is bit for bit that of the
+ * chain below.  inner [nz][iy][ix], outer [nz][oy][ox], out [nz][ty][tx].  Refused: a NULL plan, a NULL vector plan (a pair that
+ * no interpolator rotates is two scalar merges), a NULL buffer with nz > 0, a vector plan whose grid is not its regrid plan's
+ * output grid or that lives on another device than the merge plan, a calling thread on another device, an output buffer that
+ * overlaps any other buffer.  nz == 0 does nothing.  The host form is declared in fimex_amd_merge_vector_host.h.
+ */
+int fimex_amd_merge_apply_vector_device(const fimex_amd_merge_plan* plan, const fimex_amd_vector_plan* outerToInnerVec,
+                                        const fimex_amd_vector_plan* innerToTargetVec, const fimex_amd_vector_plan* outerToTargetVec,
+                                        const float* d_innerU, const float* d_innerV, const float* d_outerU, const float* d_outerV, size_t nz,
+                                        float* d_outU, float* d_outV, void* stream);
+/** The same result step by step on stream-ordered temporaries: the pair regridded and rotated three times as
+ *  fimex_amd_regrid_apply_vector_device does it, fimex_amd_border_smooth_device twice and fimex_amd_overlay_device twice.  The
+ *  cross-check and the yardstick of the fused kernels. */
+int fimex_amd_merge_apply_vector_chain_device(const fimex_amd_merge_plan* plan, const fimex_amd_vector_plan* outerToInnerVec,
+                                              const fimex_amd_vector_plan* innerToTargetVec, const fimex_amd_vector_plan* outerToTargetVec,
+                                              const float* d_innerU, const float* d_innerV, const float* d_outerU, const float* d_outerV,
+                                              size_t nz, float* d_outU, float* d_outV, void* stream);
 
 /* ------------- scaled reads and writes, theta2T, humidity, accumulate (8f n9) */
 /* The arithmetic around the entries above that the reference keeps in its readers and decorators: unpacking stored data
