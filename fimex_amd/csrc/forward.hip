@@ -15,6 +15,7 @@
 //    left-to-right float additions are kept).
 // Dense mappings take the LDS-staged kernel of forward_tiled.hip, their medians the wave kernels of forward_median.hip.
 #include "forward.hpp"
+#include "forward_launch.hpp"
 
 namespace fimex_amd {
 
@@ -170,89 +171,102 @@ __global__ void __launch_bounds__(kBlock) forward_apply_wave(FwdArgs a)
     }
 }
 
-constexpr int kLaneZc = 8;  // slices a lane reduces together (gathers in flight per lane)
+using forward_launch::Family;
+constexpr int kLaneZc = forward_launch::kLaneZc;
+static_assert((int)Aggregate::Median == forward_launch::kAggregateMedian && (uint32_t)kBlock == forward_launch::kBlock && (uint32_t)kXcds == forward_launch::kXcds,
+              "forward_launch.hpp restates the constants of plan.hpp and common.hpp");
 
+// sums and extrema (and the median of single cells as a maximum): the kernel forward_launch.hpp names
 template <Aggregate A, bool UNDEF>
-void launch_kind(const FwdArgs& a, dim3 grid, bool wavePath, bool longBuckets, hipStream_t stream)
+void launch_kind(const FwdArgs& a, const forward_launch::Launch& l, dim3 grid, hipStream_t stream)
 {
-    if (wavePath) {
+    if (l.family == Family::Wave) {
         forward_apply_wave<A, UNDEF><<<wave_grid(a, grid.y), kBlock, 0, stream>>>(a);
-    } else if (longBuckets) {
+    } else if (l.ahead == 8) {
         forward_apply_lane<A, UNDEF, kLaneZc, false, 8><<<grid, kBlock, 0, stream>>>(a);
-    } else if (a.nz == 1) {
+    } else if (l.zc == 1) {
         // one slice per call is the reference's own call pattern (src/CDMInterpolator.cc:251-259): no eight-slice passes that read
         // the one slice eight times (configs[3], one slice: see DESIGN.md 6)
         forward_apply_lane<A, UNDEF, 1><<<grid, kBlock, 0, stream>>>(a);
-    } else if (a.nz <= 2) {
+    } else if (l.zc == 2) {
         forward_apply_lane<A, UNDEF, 2><<<grid, kBlock, 0, stream>>>(a);
-    } else if (a.nz <= 4) {
+    } else if (l.zc == 4) {
         forward_apply_lane<A, UNDEF, 4><<<grid, kBlock, 0, stream>>>(a);
     } else {
         forward_apply_lane<A, UNDEF, kLaneZc><<<grid, kBlock, 0, stream>>>(a);
     }
 }
 
+// -1: not set
+forward_launch::Tuning read_tuning()
+{
+    forward_launch::Tuning t;
+    t.tiled = tuning("FWD_TILED", -1);
+    t.zpb = tuning("FWD_ZPB", -1);
+    t.wave = tuning("FWD_WAVE", -1);
+    t.medianShort = tuning("FWD_MEDIAN_SHORT", -1);
+    t.medianWaveMin = tuning("FWD_MEDIAN_WAVE_MIN", -1);
+    t.medianWave = tuning("FWD_MEDIAN_WAVE", -1);
+    t.medianZc = tuning("FWD_MEDIAN_ZC", -1);
+    return t;
+}
+
 }  // namespace
 
+// The choice of kernel and the z chunks are forward_launch.hpp's (the measurements behind its thresholds: DESIGN.md 6):
+//  * z chunks: a workgroup reads its CSR entries once per chunk, so chunks are long (the CSR of configs[3] is 10 MB, a slice's
+//    must-move bytes about the same); several chunks only where the target grid alone would not fill the chip;
+//  * wave per bucket only where the targets are too few to fill the chip with lanes: a dense mapping with many targets runs
+//    1.7-1.8 ms through the lane kernels against 6.5 (mean: the ordered fold) and 2.0 ms (max) through the wave kernels (0.1-degree
+//    global -> 1-degree global, 100 cells per bucket, 100 slices);
+//  * the median of medium buckets throughout (a source finer than the target) by one wave per target: its cost does not depend on
+//    the bucket's length (25 ms per 100 slices of a million targets), the lane kernel's rank counting grows with its square (6.3 ms
+//    at 4-9 cells, about 32 at 25): a wave per target from a mean length of twelve;
+//  * the median of buckets of at most two cells: eight slices in flight, no rank counting (four targets per lane with 16-byte stores
+//    were measured as well: 8 % slower on configs[3], the gathers lose parallelism).
 void launch_forward_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream)
 {
     if (nz == 0) return;
     FA_REQUIRE(nz <= 0xFFFFFFFFu, "too many slices");
-    if (launch_forward_tiled(plan, d_in, nz, d_out, stream)) return;  // dense mappings, all aggregates but the median
+    const size_t nOut = plan.outX * plan.outY;
+    const forward_launch::Launch l = forward_launch::forward_launch(nOut, nz, plan.info.mappedSourceCells, plan.info.undefinedCells, plan.info.maxBucket,
+                                                                    (int)plan.aggregate, plan.fwdTiles.valid, read_tuning());
+    if (l.family == Family::Tiled && launch_forward_tiled(plan, d_in, nz, d_out, stream)) return;
+    FA_REQUIRE(l.family != Family::Tiled, "the tiled forward kernel refused a plan that holds its tiles");
     FwdArgs a{};
     a.in = d_in;
     a.out = d_out;
     a.offsets = plan.offsets.get();
     a.src = plan.src.get();
-    a.nOut = (uint32_t)(plan.outX * plan.outY);
+    a.nOut = (uint32_t)nOut;
     a.inLayer = plan.inX * plan.inY;
     a.nz = (uint32_t)nz;
-    a.rankAll = tuning("FWD_MEDIAN_SHORT", 1) == 0 ? 1u : 0u;
-    // z chunks: a workgroup reads its CSR entries once per chunk, so chunks are long (the CSR of configs[3] is 10 MB, a slice's
-    // must-move bytes about the same); several chunks only where the target grid alone would not fill the chip
-    const size_t blocks = ceil_div(a.nOut, kBlock);
-    uint32_t zpb = (uint32_t)tuning("FWD_ZPB", blocks >= 4096 ? 64 : 16);
-    if (zpb > nz) zpb = (uint32_t)nz;
-    size_t chunks = ceil_div(nz, (size_t)zpb);
-    zpb = (uint32_t)ceil_div(nz, chunks);  // chunks of one size
-    a.zPerBlock = zpb;
-    chunks = ceil_div(nz, (size_t)zpb);
-    FA_REQUIRE(chunks <= 65535, "too many z chunks for one launch");
+    a.rankAll = l.rankAll ? 1u : 0u;
+    a.zPerBlock = l.zPerBlock;
+    FA_REQUIRE(l.chunksFit(), "too many z chunks for one launch");
     // the lane kernels map workgroup -> block of targets through the XCD it runs on: their grid is a multiple of 8
-    const dim3 gridLane((uint32_t)(ceil_div(blocks, (size_t)kXcds) * kXcds), (uint32_t)chunks, 1);
-    // mean bucket length decides: long buckets are reduced by a whole wave
-    const size_t nonEmpty = a.nOut - plan.info.undefinedCells;
-    const double meanBucket = nonEmpty ? (double)plan.info.mappedSourceCells / (double)nonEmpty : 0.0;
-    int waveMode = tuning("FWD_WAVE", -1);
-    // wave per bucket only where the targets are too few to fill the chip with lanes (fewer than 64 K (target, z chunk) lanes): a
-    // dense mapping with many targets runs 1.7-1.8 ms through the lane kernels against 6.5 (mean: the ordered fold) and 2.0 ms (max)
-    // through the wave kernels (0.1-degree global -> 1-degree global, 100 cells per bucket, 100 slices)
-    const bool wavePath = (waveMode < 0) ? (meanBucket >= 32.0 && (size_t)a.nOut * chunks < 65536) : (waveMode != 0);
-    const bool longBuckets = meanBucket > 4.0;  // the lane kernels with eight cells of look-ahead
+    const dim3 gridLane(l.laneGridX, (uint32_t)l.chunks, 1);
     const bool u = plan.undefAggr;
-    const auto lanes_or_waves = [&](Aggregate g, bool wave, bool ahead) {
-        with_aggregate(g, u, [&](auto A, auto U) { launch_kind<A(), U()>(a, gridLane, wave, ahead, stream); });
-    };
-    if (plan.aggregate != Aggregate::Median) {
-        lanes_or_waves(plan.aggregate, wavePath, longBuckets);
-    } else if (plan.info.maxBucket <= 1 && a.rankAll == 0) {
-        // no bucket holds more than one cell (a source grid coarser than the target, configs[3]): the median of one value is
-        // the value, which is what the max kernel returns for it bit for bit -- without the median's per-slice state
-        lanes_or_waves(Aggregate::Max, false, false);
-    } else if (a.rankAll == 0 && plan.info.maxBucket > 2 && plan.info.maxBucket <= 256 && meanBucket >= (double)tuning("FWD_MEDIAN_WAVE_MIN", 12) && tuning("FWD_MEDIAN_WAVE", 1) != 0) {
-        // medium buckets throughout (a source finer than the target): one wave per target, the median by selection on keys.  Its
-        // cost does not depend on the bucket's length (25 ms per 100 slices of a million targets), the lane kernel's rank counting
-        // grows with its square (6.3 ms at 4-9 cells, about 32 at 25): a wave per target from a mean length of twelve
+    switch (l.family) {
+    case Family::MedianAsMax:
+        with_aggregate(Aggregate::Max, u, [&](auto A, auto U) { launch_kind<A(), U()>(a, l, gridLane, stream); });
+        break;
+    case Family::MedianWave:
         launch_forward_median_wave(a, plan.info.maxBucket, u, gridLane.y, stream);
-    } else {
-        // buckets of at most two cells: eight slices in flight, no rank counting; longer ones are ranked slice by slice by the same kernel
-        // (four targets per lane with 16-byte stores were measured as well: 8 % slower on configs[3], the gathers lose parallelism)
-        const bool rank = plan.info.maxBucket > 2 || a.rankAll != 0, zc4 = tuning("FWD_MEDIAN_ZC", 8) == 4;
-        with_undef(u, [&](auto U) {
-            if (rank) forward_apply_lane<Aggregate::Median, U(), kLaneZc, true><<<gridLane, kBlock, 0, stream>>>(a);
-            else if (zc4) forward_apply_lane<Aggregate::Median, U(), 4><<<gridLane, kBlock, 0, stream>>>(a);
-            else forward_apply_lane<Aggregate::Median, U(), kLaneZc><<<gridLane, kBlock, 0, stream>>>(a);
-        });
+        break;
+    case Family::Lane:
+        if (plan.aggregate == Aggregate::Median) {
+            with_undef(u, [&](auto U) {
+                if (l.rank) forward_apply_lane<Aggregate::Median, U(), kLaneZc, true><<<gridLane, kBlock, 0, stream>>>(a);
+                else if (l.zc == 4) forward_apply_lane<Aggregate::Median, U(), 4><<<gridLane, kBlock, 0, stream>>>(a);
+                else forward_apply_lane<Aggregate::Median, U(), kLaneZc><<<gridLane, kBlock, 0, stream>>>(a);
+            });
+            break;
+        }
+        [[fallthrough]];
+    default:  // Family::Wave, and the lanes of sums and extrema
+        with_aggregate(plan.aggregate, u, [&](auto A, auto U) { launch_kind<A(), U()>(a, l, gridLane, stream); });
+        break;
     }
     FA_HIP(hipGetLastError());
 }

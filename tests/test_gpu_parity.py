@@ -183,12 +183,16 @@ def test_forward_methods_match_oracle(fa, method, density):
                                     oracle.FWD_UNDEF_SUM, oracle.FWD_UNDEF_MEAN, oracle.FWD_UNDEF_MAX, oracle.FWD_UNDEF_MIN])
 def test_forward_long_buckets_wave_path(fa, method):
     """~130 source cells per target cell: the wave-per-bucket reduction, still in the reference's add order."""
+    import forward_launch_host as flh
     inX, inY, outX, outY, nz = 400, 300, 36, 26, 3
     px, py = cases.forward_positions(inX, inY, outX, outY, seed=21, density=130.0)
     f = cases.field(nz, inY, inX, seed=90 + method, nan_frac=0.03, extremes=False)
     want = oracle.forward_interpolate_values(method, px, py, f, inX, inY, outX, outY)
     plan = fa.RegridPlan(method, px, py, inX, inY, outX, outY)
     assert plan.info()["maxBucket"] > 64
+    # forward_apply_wave it is: the launcher's own rule (csrc/forward_launch.hpp) on this plan's figures
+    launch = flh.launch_of_plan(plan.info(), nz)
+    assert launch.family == flh.WAVE, (flh.FAMILY_NAMES[launch.family], plan.info())
     got = plan.apply_host(f)
     assert cases.same(got, want), cases.describe_mismatch(got, want)
 
