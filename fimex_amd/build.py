@@ -30,8 +30,10 @@ MERGE_MATH_SHIM = os.path.join(ROOT, "tests", "merge_math_host.cc")
 
 MERGE_VECTOR_MATH_LIB = os.path.join(HERE, "libmerge_vector_math_host.so")  # csrc/merge_vector_math.hpp compiled for the CPU with g++ (tests/test_merge_vector_math_host.py)
 MERGE_VECTOR_MATH_SHIM = os.path.join(ROOT, "tests", "merge_vector_math_host.cc")
+MERGE_VECTOR_TYPED_MATH_LIB = os.path.join(HERE, "libmerge_vector_typed_math_host.so")  # csrc/merge_vector_typed_math.hpp compiled for the CPU with g++ (tests/test_merge_vector_typed_math_host.py)
+MERGE_VECTOR_TYPED_MATH_SHIM = os.path.join(ROOT, "tests", "merge_vector_typed_math_host.cc")
 
-DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_merge_typed.hip", "capi_merge_vector.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "staged2_vector_typed.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "merge_typed.hip", "merge_vector.hip", "scaled_convert.hip", "pressure_convert.hip",
+DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_merge_typed.hip", "capi_merge_vector.hip", "capi_merge_vector_typed.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "staged2_vector_typed.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "merge_typed.hip", "merge_vector.hip", "merge_vector_typed.hip", "scaled_convert.hip", "pressure_convert.hip",
                   "time_accumulate.hip", "time_interpolate.hip", "quality.hip", "extract.hip", "vertical_plan.hip"]
 
 # -ffp-contract=off: the kernels reproduce the reference's IEEE arithmetic operation by operation
@@ -55,7 +57,7 @@ def _newer(target, deps):
 
 def _headers():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    hdrs += [os.path.join(ROOT, "include", h) for h in ("fimex_amd.h", "fimex_amd_derived_host.h", "fimex_amd_time_quality_host.h", "fimex_amd_extract_host.h", "fimex_amd_vertical_plan_host.h", "fimex_amd_vector_regrid_host.h", "fimex_amd_vector_regrid_typed_host.h", "fimex_amd_merge_typed_host.h", "fimex_amd_merge_vector_host.h")]
+    hdrs += [os.path.join(ROOT, "include", h) for h in ("fimex_amd.h", "fimex_amd_derived_host.h", "fimex_amd_time_quality_host.h", "fimex_amd_extract_host.h", "fimex_amd_vertical_plan_host.h", "fimex_amd_vector_regrid_host.h", "fimex_amd_vector_regrid_typed_host.h", "fimex_amd_merge_typed_host.h", "fimex_amd_merge_vector_host.h", "fimex_amd_merge_vector_typed_host.h")]
     return hdrs
 
 
@@ -179,10 +181,24 @@ def build_merge_vector_math_host(force=False):
     return MERGE_VECTOR_MATH_LIB
 
 
+def build_merge_vector_typed_math_host(force=False):
+    """The merge's per-cell arithmetic on a vector pair in its stored types (csrc/merge_vector_typed_math.hpp), with g++ and no HIP header: the tests run it on the CPU."""
+    deps = [MERGE_VECTOR_TYPED_MATH_SHIM] + [os.path.join(CSRC, h) for h in ("merge_vector_typed_math.hpp", "merge_vector_math.hpp", "merge_math.hpp")]
+    if force or _newer(MERGE_VECTOR_TYPED_MATH_LIB, deps):
+        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC, MERGE_VECTOR_TYPED_MATH_SHIM, "-o",
+               MERGE_VECTOR_TYPED_MATH_LIB]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError("merge vector typed math shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
+        if r.stderr.strip():
+            sys.stderr.write(r.stderr)
+    return MERGE_VECTOR_TYPED_MATH_LIB
+
+
 def clean():
     """Removes every built artefact, so that the next build starts from the sources alone."""
     shutil.rmtree(OBJ, ignore_errors=True)
-    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, STENCIL_LIB, PROJECTION_LIB, FORWARD_MATH_LIB, MERGE_MATH_LIB, MERGE_VECTOR_MATH_LIB, os.path.join(HERE, "host_cli.so")):
+    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, STENCIL_LIB, PROJECTION_LIB, FORWARD_MATH_LIB, MERGE_MATH_LIB, MERGE_VECTOR_MATH_LIB, MERGE_VECTOR_TYPED_MATH_LIB, os.path.join(HERE, "host_cli.so")):
         if os.path.exists(f):
             os.remove(f)
 
@@ -198,6 +214,7 @@ def build_all(force=False, jobs=4):
     build_forward_math_host(force=force)
     build_merge_math_host(force=force)
     build_merge_vector_math_host(force=force)
+    build_merge_vector_typed_math_host(force=force)
     return lib, host
 
 

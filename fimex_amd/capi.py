@@ -214,6 +214,9 @@ SYMBOLS = {
     "fimex_amd_merge_apply_typed_chain_device": (ctypes.c_int, [_V, _V, _PK, _V, _PK, _Z, _V, _V]),
     "fimex_amd_merge_apply_vector_device": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _V, _V]),
     "fimex_amd_merge_apply_vector_chain_device": (ctypes.c_int, [_V, _V, _V, _V, _V, _V, _V, _V, _Z, _V, _V, _V]),
+    "fimex_amd_merge_apply_vector_typed_device": (ctypes.c_int, [_V, _V, _V, _V, _V, _PK, _V, _PK, _V, _PK, _V, _PK, _Z, _V, _V, _V,
+                                                                 ctypes.POINTER(ctypes.c_int)]),
+    "fimex_amd_merge_apply_vector_typed_chain_device": (ctypes.c_int, [_V, _V, _V, _V, _V, _PK, _V, _PK, _V, _PK, _V, _PK, _Z, _V, _V, _V]),
     "fimex_amd_project_values_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z]),
     "fimex_amd_project_values_device": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _V, _V, _Z, _V]),
     "fimex_amd_project_axes_host": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_char_p, _D, _D, _Z, _Z, _D, _D]),
@@ -282,6 +285,12 @@ MERGE_VECTOR_HOST_SYMBOLS = {
     "fimex_amd_merge_apply_vector_host": (ctypes.c_int, [_V, _V, _V, _V, _F, _F, _F, _F, _Z, _F, _F]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_merge_vector_typed_host.h declares: the merge of an x/y vector pair in
+# its stored types on host buffers
+MERGE_VECTOR_TYPED_HOST_SYMBOLS = {
+    "fimex_amd_merge_apply_vector_typed_host": (ctypes.c_int, [_V, _V, _V, _V, _V, _PK, _V, _PK, _V, _PK, _V, _PK, _Z, _V, _V]),
+}
+
 # name -> (restype, argtypes); every symbol include/fimex_amd_vertical_plan_host.h declares: the entries of (8f n5b) on host buffers
 VERTICAL_PLAN_HOST_SYMBOLS = {
     "fimex_amd_vertical_plan_create_host": (ctypes.c_int, [ctypes.c_int, _Z, _Z, _Z, ctypes.POINTER(VerticalLevelsStruct),
@@ -306,7 +315,8 @@ def _open(path):
     lib = ctypes.CDLL(path)
     for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
             EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()) + list(VECTOR_REGRID_HOST_SYMBOLS.items()) + list(
-            VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()) + list(MERGE_TYPED_HOST_SYMBOLS.items()) + list(MERGE_VECTOR_HOST_SYMBOLS.items()):
+            VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()) + list(MERGE_TYPED_HOST_SYMBOLS.items()) + list(MERGE_VECTOR_HOST_SYMBOLS.items()) + list(
+            MERGE_VECTOR_TYPED_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1378,6 +1388,49 @@ class MergePlan:
         outU, outV = (np.empty((nz, self.outY, self.outX), dtype=np.float32) for _ in range(2))
         _check(load().fimex_amd_merge_apply_vector_host(self._h, outerToInnerVec._h, innerToTargetVec._h, outerToTargetVec._h, _fp(iu), _fp(iv),
                                                         _fp(ou), _fp(ov), nz, _fp(outU), _fp(outV)))
+        return outU, outV
+
+    def _vector_typed_args(self, vecs, fields, nz, outs):
+        """(plan, three vector plans, pointer and packing of inner u, inner v, outer u, outer v, nz, outU, outV) of the C entries"""
+        pairs = [x for ptr, packing in fields for x in (ptr, ctypes.byref(packing))]
+        return [self._h] + [v._h for v in vecs] + pairs + [nz] + list(outs)
+
+    def apply_vector_typed_device(self, outerToInnerVec, innerToTargetVec, outerToTargetVec, d_innerU, innerUPacking, d_innerV, innerVPacking,
+                                  d_outerU, outerUPacking, d_outerV, outerVPacking, nz, d_outU, d_outV, stream=0):
+        """The merge of an x/y vector pair whose four fields are in their stored types, each with its Packing; the rotations act on
+        the raw counts.  d_outU holds inner u's type in inner u's packing, d_outV inner v's.  Returns the path: 1 the two fused
+        kernels, 0 the chain of apply_vector_typed_chain_device."""
+        path = ctypes.c_int(-1)
+        args = self._vector_typed_args((outerToInnerVec, innerToTargetVec, outerToTargetVec),
+                                       ((d_innerU, innerUPacking), (d_innerV, innerVPacking), (d_outerU, outerUPacking), (d_outerV, outerVPacking)),
+                                       nz, (d_outU, d_outV))
+        _check(load().fimex_amd_merge_apply_vector_typed_device(*args, stream, ctypes.byref(path)))
+        return path.value
+
+    def apply_vector_typed_chain_device(self, outerToInnerVec, innerToTargetVec, outerToTargetVec, d_innerU, innerUPacking, d_innerV, innerVPacking,
+                                        d_outerU, outerUPacking, d_outerV, outerVPacking, nz, d_outU, d_outV, stream=0):
+        """The same step by step: the pair regridded and rotated three times on its stored types, the typed smoothing and the typed
+        overlay once per component (cross-check and yardstick of the fused kernels; every numeric type, components of different types)."""
+        args = self._vector_typed_args((outerToInnerVec, innerToTargetVec, outerToTargetVec),
+                                       ((d_innerU, innerUPacking), (d_innerV, innerVPacking), (d_outerU, outerUPacking), (d_outerV, outerVPacking)),
+                                       nz, (d_outU, d_outV))
+        _check(load().fimex_amd_merge_apply_vector_typed_chain_device(*args, stream))
+
+    def apply_vector_typed_host(self, outerToInnerVec, innerToTargetVec, outerToTargetVec, innerU, innerUPacking, innerV, innerVPacking, outerU,
+                                outerUPacking, outerV, outerVPacking):
+        """The same on host arrays in their stored types: inner [nz][iy][ix] and outer [nz][oy][ox] components -> (outU, outV), each
+        [nz][ty][tx] in its inner component's type."""
+        oi = self._plans[0]
+        iu, iv, ou, ov = (_typed(a, p).ravel() for a, p in ((innerU, innerUPacking), (innerV, innerVPacking), (outerU, outerUPacking),
+                                                            (outerV, outerVPacking)))
+        nz = iu.size // (oi.outX * oi.outY)
+        if iu.size != nz * oi.outX * oi.outY or iv.size != iu.size or ou.size != nz * oi.inX * oi.inY or ov.size != ou.size:
+            raise ValueError("the four components do not hold the same number of whole slices")
+        outU, outV = (np.empty((nz, self.outY, self.outX), dtype=a.dtype) for a in (iu, iv))
+        args = self._vector_typed_args((outerToInnerVec, innerToTargetVec, outerToTargetVec),
+                                       ((iu.ctypes.data, innerUPacking), (iv.ctypes.data, innerVPacking), (ou.ctypes.data, outerUPacking),
+                                        (ov.ctypes.data, outerVPacking)), nz, (outU.ctypes.data, outV.ctypes.data))
+        _check(load().fimex_amd_merge_apply_vector_typed_host(*args))
         return outU, outV
 
 

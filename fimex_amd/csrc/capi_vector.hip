@@ -30,6 +30,25 @@ int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_
     return 0;
 }
 
+// CDMInterpolator.cc:251-285 on device buffers in the components' stored types: the kernel on the stored type (path 2) where it
+// serves the pair, else the chain it replaces -- to float, the float pair, back to the stored types -- on temporaries that are
+// released after the stream has been waited for; returns the path taken (the chain: what apply_vector_pair took).  Declared in
+// plan.hpp: the chain of merge_vector_typed.hip runs it too
+int apply_vector_pair_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, int uType, double uBad,
+                            const void* d_v, int vType, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream)
+{
+    if (uType == vType && launch_staged2_apply_vector_typed(plan, vec, d_u, d_v, uType, uBad, vBad, nz, d_uOut, d_vOut, stream)) return 2;
+    const size_t nIn = nz * plan.inX * plan.inY, nOut = nz * plan.outX * plan.outY;
+    DeviceArray<float> fu(nIn), fv(nIn), fuOut(nOut), fvOut(nOut);
+    launch_data2interpolation(d_u, uType, nIn, uBad, fu.get(), stream);
+    launch_data2interpolation(d_v, vType, nIn, vBad, fv.get(), stream);
+    const int taken = apply_vector_pair(plan, vec, fu.get(), fv.get(), nz, fuOut.get(), fvOut.get(), stream);
+    launch_interpolation2data(fuOut.get(), nOut, uType, uBad, d_uOut, stream);
+    launch_interpolation2data(fvOut.get(), nOut, vType, vBad, d_vOut, stream);
+    FA_HIP(hipStreamSynchronize(stream));  // the temporaries are released on return
+    return taken;
+}
+
 }  // namespace fimex_amd
 
 namespace {
@@ -102,24 +121,6 @@ void check_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector
                        const float* uOut, const float* vOut)
 {
     check_vector_pair_sized(plan, vec, u, sizeof(float), v, sizeof(float), nz, uOut, vOut);
-}
-
-// CDMInterpolator.cc:251-285 on device buffers in the components' stored types: the kernel on the stored type (path 2) where it
-// serves the pair, else the chain it replaces -- to float, the float pair, back to the stored types -- on temporaries that are
-// released after the stream has been waited for; returns the path taken (the chain: what apply_vector_pair took)
-int apply_vector_pair_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, int uType, double uBad,
-                            const void* d_v, int vType, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream)
-{
-    if (uType == vType && launch_staged2_apply_vector_typed(plan, vec, d_u, d_v, uType, uBad, vBad, nz, d_uOut, d_vOut, stream)) return 2;
-    const size_t nIn = nz * plan.inX * plan.inY, nOut = nz * plan.outX * plan.outY;
-    DeviceArray<float> fu(nIn), fv(nIn), fuOut(nOut), fvOut(nOut);
-    launch_data2interpolation(d_u, uType, nIn, uBad, fu.get(), stream);
-    launch_data2interpolation(d_v, vType, nIn, vBad, fv.get(), stream);
-    const int taken = apply_vector_pair(plan, vec, fu.get(), fv.get(), nz, fuOut.get(), fvOut.get(), stream);
-    launch_interpolation2data(fuOut.get(), nOut, uType, uBad, d_uOut, stream);
-    launch_interpolation2data(fvOut.get(), nOut, vType, vBad, d_vOut, stream);
-    FA_HIP(hipStreamSynchronize(stream));  // the temporaries are released on return
-    return taken;
 }
 
 }  // namespace

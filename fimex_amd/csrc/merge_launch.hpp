@@ -1,6 +1,7 @@
-// Launch geometry shared by the merge kernels on float arrays (merge.hip), on stored types (merge_typed.hip) and on float vector
-// pairs (merge_vector.hip): the tile of a workgroup, the slices in flight per lane, the grid over tiles and chunks of slices, the
-// stencil size of a backward plan, and for the two float files a plan's arrays as kernel arguments and the call's scratch.
+// Launch geometry shared by the merge kernels on float arrays (merge.hip), on stored types (merge_typed.hip), on float vector
+// pairs (merge_vector.hip) and on packed vector pairs (merge_vector_typed.hip): the tile of a workgroup, the slices in flight per
+// lane, the grid over tiles and chunks of slices, the stencil size of a backward plan, for the two float files a plan's arrays as
+// kernel arguments and the call's scratch, and for the two pair files the pair-slices in flight and a rotation's lazy read.
 #pragma once
 
 #include "gather_entry.hpp"
@@ -12,6 +13,28 @@ namespace merge_launch {
 constexpr int kTileX = 64, kTileY = 4;  // a wave per row
 static_assert(kTileX * kTileY == kBlock, "a tile is one workgroup");
 constexpr int kAhead = 4;               // slices whose loads are in flight together
+
+// ---- the kernels on a vector pair (merge_vector.hip, merge_vector_typed.hip)
+// pair-slices in flight per lane: a bicubic entry holds 2 x 16 taps per pair-slice and combines them in double
+template <int STENCIL>
+constexpr int ahead_of() { return STENCIL == 4 ? 1 : STENCIL == 2 ? 2 : 4; }
+static_assert(kAhead % ahead_of<1>() == 0 && kAhead % ahead_of<2>() == 0, "a z chunk is a whole number of groups");
+
+// (m0, m1) of one cell of a rotation, read at first use
+struct LazyMatrix {
+    const double2* cs;
+    uint32_t cell;
+    bool have = false;
+    double2 m = {0., 0.};
+    __device__ __forceinline__ const double2& get()
+    {
+        if (!have) {
+            m = cs[cell];
+            have = true;
+        }
+        return m;
+    }
+};
 
 // tiles of one slice in x and y, chunks of slices in z: enough workgroups to fill the device, chunks long enough to amortise the
 // per-cell set-up (class, plan entries)

@@ -19,36 +19,17 @@ namespace fimex_amd {
 
 namespace {
 
+using merge_launch::ahead_of;
 using merge_launch::FloatScratch;
 using merge_launch::kTileX;
 using merge_launch::kTileY;
+using merge_launch::LazyMatrix;
 using merge_launch::plan_ref;
 using merge_launch::PlanRef;
 using merge_launch::stencil_of;
 using merge_launch::tile_grid;
 using merge_math::Pair;
 using merge_math::SmoothClass;
-
-// pair-slices in flight per lane: a bicubic entry holds 2 x 16 taps per pair-slice and combines them in double
-template <int STENCIL>
-constexpr int ahead_of() { return STENCIL == 4 ? 1 : STENCIL == 2 ? 2 : 4; }
-static_assert(merge_launch::kAhead % ahead_of<1>() == 0 && merge_launch::kAhead % ahead_of<2>() == 0, "a z chunk is a whole number of groups");
-
-// (m0, m1) of one cell of a rotation, read at first use
-struct LazyMatrix {
-    const double2* cs;
-    uint32_t cell;
-    bool have = false;
-    double2 m = {0., 0.};
-    __device__ __forceinline__ const double2& get()
-    {
-        if (!have) {
-            m = cs[cell];
-            have = true;
-        }
-        return m;
-    }
-};
 
 // both components of one slice through one decoded entry, rotated
 template <int STENCIL>

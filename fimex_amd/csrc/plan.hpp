@@ -315,6 +315,20 @@ void launch_merge_vector_chain(const fimex_amd_merge_plan& m, const fimex_amd_ve
                                const fimex_amd_vector_plan& rotOT, const float* d_innerU, const float* d_innerV, const float* d_outerU,
                                const float* d_outerV, size_t nz, float* d_outU, float* d_outV, hipStream_t stream);
 
+// merge_vector_typed.hip: the same on an x/y vector pair in its stored types; every one of the four fields has its own packing,
+// outU has inner u's, outV inner v's.  launch_merge_vector_typed_fused returns false, with nothing launched, where the fused
+// kernels do not serve the call
+struct PackedVectorFields {
+    const void *d_innerU, *d_innerV, *d_outerU, *d_outerV;
+    fimex_amd_packing innerUPacking, innerVPacking, outerUPacking, outerVPacking;
+};
+bool launch_merge_vector_typed_fused(const fimex_amd_merge_plan& m, const fimex_amd_vector_plan& rotOI, const fimex_amd_vector_plan& rotST,
+                                     const fimex_amd_vector_plan& rotOT, const PackedVectorFields& in, size_t nz, void* d_outU, void* d_outV,
+                                     hipStream_t stream);
+void launch_merge_vector_typed_chain(const fimex_amd_merge_plan& m, const fimex_amd_vector_plan& rotOI, const fimex_amd_vector_plan& rotST,
+                                     const fimex_amd_vector_plan& rotOT, const PackedVectorFields& in, size_t nz, void* d_outU, void* d_outV,
+                                     hipStream_t stream);
+
 // projection.hip: pj_transform-level plan building on the device (strings: projection_parse.hip, point math: proj_math.hpp)
 void launch_project_values(const char* projIn, const char* projOut, double* d_x, double* d_y, size_t n, hipStream_t stream);
 void launch_project_axes(const char* projIn, const char* projOut, const double* h_xAxis, const double* h_yAxis, size_t ix, size_t iy,
@@ -352,6 +366,10 @@ void apply_plan_device(const fimex_amd_regrid_plan& plan, const float* d_in, siz
 // capi_vector.hip: a vector pair regridded and rotated as fimex_amd_regrid_apply_vector_device serves it; returns the path taken
 int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
                       float* d_uOut, float* d_vOut, hipStream_t stream);
+// the same on the components' stored types as fimex_amd_regrid_apply_vector_typed_device serves it (the chain of
+// merge_vector_typed.hip runs it too)
+int apply_vector_pair_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, int uType, double uBad,
+                            const void* d_v, int vType, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream);
 
 // hostpipe.hip: streamed transfers for the *_host entry points
 using SliceChunkFn = std::function<void(const void* dRawIn, void* dRawOut, float* dFIn, float* dFOut, size_t nzc, hipStream_t stream)>;

@@ -657,7 +657,7 @@ int fimex_amd_omega_to_vertical_wind_host(const fimex_amd_vertical_levels* press
  * stored as float with scale 1 and offset 0 (a double variable is narrowed to float before the blend of step 2 here, after it in
  * the reference).  Packed variables, and every variable in its stored type, take the *_typed entries at the end of this block.
  * An x/y vector pair, which every interpolator of the merger rotates behind its regrid, takes fimex_amd_merge_apply_vector_device
- * behind the typed entries; packed pairs go step by step through the typed entries. */
+ * behind the typed entries, a packed pair fimex_amd_merge_apply_vector_typed_device behind that (6.17). */
 /**
  * CDMBorderSmoothing::getDataSlice (src/CDMBorderSmoothing.cc:129-139) with CDMBorderSmoothing_Linear::operator()
  * (src/CDMBorderSmoothing_Linear.cc:41-85) on [nz][ny][nx] slices: an undefined inner value gives the outer one
@@ -774,6 +774,43 @@ int fimex_amd_merge_apply_vector_chain_device(const fimex_amd_merge_plan* plan, 
                                               const fimex_amd_vector_plan* innerToTargetVec, const fimex_amd_vector_plan* outerToTargetVec,
                                               const float* d_innerU, const float* d_innerV, const float* d_outerU, const float* d_outerV,
                                               size_t nz, float* d_outU, float* d_outV, void* stream);
+
+/**
+ * CDMMerger::getDataSlice on an x/y vector pair whose four fields -- inner u, inner v, outer u, outer v -- are in their stored
+ * types, each with its own fimex_amd_packing: the typed merge and the vector merge above taken together.
+ * regridRotT(plan, R; U, pU, V, pV) is fimex_amd_regrid_apply_vector_typed_device: both components read as raw counts with the
+ * own fill value as NaN, regridded, rotated on the counts, each written back in its own type with its own fill value.
+ *   1  (OIu, OIv) = regridRotT(outerToInner, R_oi; outerU, outerV)
+ *   2  Su = pack_Iu(smooth(unpack_Iu(innerU), unpack_Ou(OIu))), Sv likewise with the v packings      blended in double
+ *   3  (STu, STv) = regridRotT(innerToTarget, R_st; Su, Sv),  (OTu, OTv) = regridRotT(outerToTarget, R_ot; outerU, outerV)
+ *   4  outU = pack_Iu(isnan(unpack_Iu(STu)) ? unpack_Ou(OTu) : unpack_Iu(STu)), outV likewise
+ * The rotation acts on counts, as the reference's does: an add_offset is not rotated with the value, and two components with
+ * different scales are rotated as if they had one.  An undefined count in either regridded component, or a NaN matrix cell, makes
+ * both rotated components the fill value; a rotated count outside the type's range wraps (long -> int -> T), it is not clamped.
+ * d_outU [nz][ty][tx] has inner u's type and packing, d_outV inner v's.  *path (may be NULL; written as 0 before any check): 1 the
+ * two fused kernels ran (all four fields short, or all unsigned short; the six buffers aligned to 2 bytes; all four fill values
+ * representable in the type), 0 the chain below ran inside the entry.  Same results either way.  Refused: a NULL plan, vector
+ * plan or packing, a NULL buffer with nz > 0, a type without element size (NAT, STRING), an inner fill value that is not
+ * representable in its type, a vector plan whose grid is not its regrid plan's output grid or that lives on another device than
+ * the merge plan, a calling thread on another device, an output buffer that overlaps any other buffer (sizes counted in each
+ * buffer's own element size).  nz == 0 does nothing.  The host form is declared in fimex_amd_merge_vector_typed_host.h.
+ */
+int fimex_amd_merge_apply_vector_typed_device(const fimex_amd_merge_plan* plan, const fimex_amd_vector_plan* outerToInnerVec,
+                                              const fimex_amd_vector_plan* innerToTargetVec, const fimex_amd_vector_plan* outerToTargetVec,
+                                              const void* d_innerU, const fimex_amd_packing* innerUPacking, const void* d_innerV,
+                                              const fimex_amd_packing* innerVPacking, const void* d_outerU, const fimex_amd_packing* outerUPacking,
+                                              const void* d_outerV, const fimex_amd_packing* outerVPacking, size_t nz, void* d_outU, void* d_outV,
+                                              void* stream, int* path);
+/** The same result step by step on stream-ordered temporaries of the stored types: the pair regridded and rotated three times as
+ *  fimex_amd_regrid_apply_vector_typed_device does it, fimex_amd_border_smooth_typed_device twice and
+ *  fimex_amd_overlay_typed_device twice.  Serves all ten numeric types and components of different types.  The cross-check and
+ *  the yardstick of the fused kernels. */
+int fimex_amd_merge_apply_vector_typed_chain_device(const fimex_amd_merge_plan* plan, const fimex_amd_vector_plan* outerToInnerVec,
+                                                    const fimex_amd_vector_plan* innerToTargetVec, const fimex_amd_vector_plan* outerToTargetVec,
+                                                    const void* d_innerU, const fimex_amd_packing* innerUPacking, const void* d_innerV,
+                                                    const fimex_amd_packing* innerVPacking, const void* d_outerU,
+                                                    const fimex_amd_packing* outerUPacking, const void* d_outerV,
+                                                    const fimex_amd_packing* outerVPacking, size_t nz, void* d_outU, void* d_outV, void* stream);
 
 /* ------------- scaled reads and writes, theta2T, humidity, accumulate (8f n9) */
 /* The arithmetic around the entries above that the reference keeps in its readers and decorators: unpacking stored data
