@@ -33,7 +33,8 @@ class PlanInfo(ctypes.Structure):
                 ("inX", ctypes.c_size_t), ("inY", ctypes.c_size_t), ("outX", ctypes.c_size_t), ("outY", ctypes.c_size_t),
                 ("planBytes", ctypes.c_size_t), ("undefinedCells", ctypes.c_size_t), ("borderCells", ctypes.c_size_t),
                 ("maxBucket", ctypes.c_size_t), ("mappedSourceCells", ctypes.c_size_t),
-                ("stagedCells", ctypes.c_size_t), ("tileW", ctypes.c_size_t), ("tileH", ctypes.c_size_t)]
+                ("stagedCells", ctypes.c_size_t), ("tileW", ctypes.c_size_t), ("tileH", ctypes.c_size_t),
+                ("launchOrder", ctypes.c_size_t)]
 
 
 BATCH_MAX_POSITIONS = 16
@@ -117,6 +118,7 @@ SYMBOLS = {
     "fimex_amd_regrid_apply_host": (ctypes.c_int, [_V, _F, _Z, _F, _Z, _ZP]),
     "fimex_amd_regrid_apply_device": (ctypes.c_int, [_V, _V, _Z, _V, _V]),
     "fimex_amd_regrid_plan_tune_device": (ctypes.c_int, [_V, _V, _Z, _V, _V, ctypes.POINTER(ctypes.c_int)]),
+    "fimex_amd_regrid_plan_launch_order": (ctypes.c_int, [_V, _Z, ctypes.POINTER(ctypes.c_int)]),
     "fimex_amd_regrid_apply_gather_device": (ctypes.c_int, [_V, _V, _Z, _V, _V]),
     "fimex_amd_regrid_batch_alloc_device": (ctypes.c_int, [_V, _V, _Z, ctypes.c_int, _V, ctypes.POINTER(_V)]),
     "fimex_amd_regrid_source_batch_alloc_device": (ctypes.c_int, [_V, _Z, ctypes.c_int, _V, ctypes.POINTER(_V)]),
@@ -491,6 +493,13 @@ class RegridPlan:
         chosen = ctypes.c_int(0)
         _check(load().fimex_amd_regrid_plan_tune_device(self._h, d_in, nz, d_out, stream, ctypes.byref(chosen)))
         return chosen.value
+
+    def launch_order(self, nz):
+        """The launch order apply_device runs nz float slices in: 1 an XCD runs whole tiles, 2 an XCD runs one z chunk of every tile
+        (info()["launchOrder"] == 1 and a batch long enough), 0 chunk-major (tuning build), -1 not the second staged form."""
+        order = ctypes.c_int(-1)
+        _check(load().fimex_amd_regrid_plan_launch_order(self._h, nz, ctypes.byref(order)))
+        return order.value
 
 
 class Batch:

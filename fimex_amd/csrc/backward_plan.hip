@@ -135,14 +135,25 @@ void build_backward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const 
     }
 }
 
+// whether a float batch of nz slices takes the second staged form:
+// the staged kernel pays a per-tile set-up (row table, chunk list) that only amortises over a few slices
+// (a bicubic plan in the reference's arithmetic that holds both forms runs the first one)
+static bool takes_second_form(const fimex_amd_regrid_plan& plan, size_t nz)
+{
+    const bool second = plan.staged2.valid && (plan.kind != PlanKind::Bicubic || plan.bicubicFast || !plan.staged.valid || tuning("STAGED2", 1) >= 2);
+    return second && tuning("STAGED", 1) != 0 && tuning("STAGED2", 1) != 0 && nz >= staged_min_nz();
+}
+
+int backward_launch_order(const fimex_amd_regrid_plan& plan, size_t nz)
+{
+    return takes_second_form(plan, nz) ? staged2_float_launch_order(plan, nz) : -1;
+}
+
 void launch_backward_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream)
 {
     if (nz == 0) return;
     FA_REQUIRE(nz <= 0xFFFFFFFFu, "too many slices");
-    // the staged kernel pays a per-tile set-up (row table, chunk list) that only amortises over a few slices
-    // (a bicubic plan in the reference's arithmetic that holds both forms runs the first one)
-    const bool second = plan.staged2.valid && (plan.kind != PlanKind::Bicubic || plan.bicubicFast || !plan.staged.valid || tuning("STAGED2", 1) >= 2);
-    if (second && tuning("STAGED", 1) != 0 && tuning("STAGED2", 1) != 0 && nz >= staged_min_nz()) {
+    if (takes_second_form(plan, nz)) {
         launch_staged2_apply(plan, d_in, nz, d_out, stream);
         return;
     }

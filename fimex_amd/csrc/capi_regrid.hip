@@ -206,20 +206,22 @@ int fimex_amd_regrid_plan_tune_device(fimex_amd_regrid_plan* plan, const float* 
     return c_guard([&] {
         FA_REQUIRE(plan != nullptr, "NULL plan");
         if (chosenShape) *chosenShape = plan->useAlt;
-        // nothing to choose between: no second shape, or a batch that takes the gather kernels anyway (the choice made for the
-        // long batches stays as it is)
-        if (nz < staged_min_nz() || !plan->staged2Alt.valid || !plan->staged2.valid) return;
+        // nothing to choose between: a batch that takes the gather kernels anyway, or neither a second shape nor a batch long enough
+        // for the second launch order (the choices made on a longer batch stay as they are).  A batch that has two shapes but is too
+        // short for the second order chooses the shape again and leaves the order alone: its own launches do not read it.
+        const bool shapes = plan->staged2Alt.valid;
+        const bool orders = backward_launch_order(*plan, nz) >= 0 && chunk_xcd_chunk_count(nz, staged2_zpb()) != 0;
+        if (nz < staged_min_nz() || !plan->staged2.valid || !(shapes || orders)) return;
         FA_REQUIRE(d_in != nullptr && d_out != nullptr, "NULL device buffer");
         require_current_device(plan->device);
         hipStream_t st = as_stream(stream);
         ScopedEvent e0, e1;
-        struct DefaultShapeOnError {  // a failed timing leaves the default shape selected
+        struct DefaultShapeOnError {  // a failed timing leaves the default shape and order selected
             fimex_amd_regrid_plan* plan;
-            ~DefaultShapeOnError() { if (plan) plan->useAlt = 0; }
+            ~DefaultShapeOnError() { if (plan) plan->useAlt = plan->chunkXcd = 0; }
         } onError{plan};
-        float best[2] = {0.f, 0.f};
-        for (int shape = 0; shape < 2; ++shape) {
-            plan->useAlt = shape;
+        if (orders) plan->chunkXcd = 0;  // the shapes are timed in the default order
+        auto median_ms = [&] {
             std::vector<float> ms;
             for (int rep = 0; rep < 7; ++rep) {  // two launches to settle, five timed: the median counts
                 FA_HIP(hipEventRecord(e0.e, st));
@@ -231,16 +233,34 @@ int fimex_amd_regrid_plan_tune_device(fimex_amd_regrid_plan* plan, const float* 
                 if (rep >= 2) ms.push_back(t);
             }
             std::sort(ms.begin(), ms.end());
-            best[shape] = ms[ms.size() / 2];
+            return ms[ms.size() / 2];
+        };
+        float best[2] = {0.f, 0.f};
+        for (int shape = 0; shape < (shapes ? 2 : 1); ++shape) {
+            plan->useAlt = shape;
+            best[shape] = median_ms();
+        }
+        plan->useAlt = shapes && best[1] < 0.99f * best[0] ? 1 : 0;  // the default shape unless the other one is clearly faster
+        if (orders) {  // then the chunk-per-XCD order on the winning shape, by the same rule
+            plan->chunkXcd = 1;
+            plan->chunkXcd = median_ms() < 0.99f * best[plan->useAlt] ? 1 : 0;
         }
         onError.plan = nullptr;
-        plan->useAlt = best[1] < 0.99f * best[0] ? 1 : 0;  // the default shape unless the other one is clearly faster
+        plan->info.launchOrder = (size_t)plan->chunkXcd;
         const auto& s = plan->useAlt ? plan->staged2Alt : plan->staged2;
         plan->info.planBytes = plan->planBytesShape[plan->useAlt];
         plan->info.stagedCells = s.stagedCells;
         plan->info.tileW = s.tileWMax;
         plan->info.tileH = s.tileH;
         if (chosenShape) *chosenShape = plan->useAlt;
+    });
+}
+
+int fimex_amd_regrid_plan_launch_order(const fimex_amd_regrid_plan* plan, size_t nz, int* order)
+{
+    return c_guard([&] {
+        FA_REQUIRE(plan != nullptr && order != nullptr, "NULL argument");
+        *order = plan->kind == PlanKind::Forward ? -1 : backward_launch_order(*plan, nz);
     });
 }
 

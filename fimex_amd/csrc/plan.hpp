@@ -59,6 +59,7 @@ struct Staged2Plan {
     size_t stagedCells = 0, totalChunks = 0;
     DeviceArray<StagedTile> tiles;
     DeviceArray<uint32_t> order;     // workgroup -> tile, ~0u = none (tile rows dealt to the XCDs in stripes)
+    DeviceArray<uint32_t> orderChunkXcd;  // the nTiles entries every XCD walks in the chunk-per-XCD order (chunk_xcd_order)
     DeviceArray<uint32_t> chunkOff;  // source cell offset of every chunk inside a slice
     DeviceArray<uint32_t> ldsA, ldsB;
 };
@@ -101,6 +102,10 @@ struct fimex_amd_regrid_plan {
     fimex_amd::Staged2Plan staged2Alt;
     int useAlt = 0;
     size_t planBytesShape[2] = {0, 0};  // info.planBytes with either shape
+    // The launch order of float batches long enough for it (chunk_xcd_chunk_count, staged_layout.hpp): 0 an XCD owns whole tiles,
+    // 1 an XCD owns z chunks of every tile.  Same results bit for bit; fimex_amd_regrid_plan_tune_device times the second one too
+    // and keeps it where it is clearly faster (info.launchOrder says which).
+    int chunkXcd = 0;
 
     // The second staged form for slices of 1- and 2-byte stored types (staged2_typed.hip): built from this plan's own arrays on the
     // first typed apply of that element size, under the mutex (plans are shared by threads; everything else is immutable).
@@ -148,6 +153,8 @@ namespace fimex_amd {
 // backward_plan.hip: classification, and the choice between the staged forms and the gather
 void build_backward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
 void launch_backward_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+// the LaunchOrder (staged_layout.hpp) of launch_backward_apply's launch of nz slices; -1: not a float launch of the second staged form
+int backward_launch_order(const fimex_amd_regrid_plan& plan, size_t nz);
 bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                         hipStream_t stream);
 // gather.hip: the per-lane gather kernel on float slices and on stored types
@@ -165,6 +172,7 @@ bool launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_
 bool build_staged2_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
 // staged2.hip
 void launch_staged2_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+int staged2_float_launch_order(const fimex_amd_regrid_plan& plan, size_t nz);  // the LaunchOrder launch_staged2_apply runs nz slices in
 // staged2_vector.hip: both components of a vector pair regridded and rotated in one launch; `serves` is the dispatch rule
 // (nearest / bilinear plans with the second staged form, batches of staged_min_nz() pairs and more, VECTOR_FUSED not 0)
 bool staged2_vector_serves(const fimex_amd_regrid_plan& plan, size_t nz);
@@ -387,5 +395,9 @@ int tuning(const char* name, int fallback);
 // batches shorter than this take the gather kernels: the staged kernels pay a per-tile set-up (chunk list, per-output plan)
 // that only amortises over a few slices (launch_backward_apply and fimex_amd_regrid_plan_tune_device share the rule)
 inline size_t staged_min_nz() { return (size_t)tuning("STAGED_MIN_NZ", 4); }
+
+// slices per z chunk of the second form's float launches in tile-major and chunk-per-XCD order (staged2_z_chunks, staged2.hpp, and
+// fimex_amd_regrid_plan_tune_device share it)
+inline uint32_t staged2_zpb() { return (uint32_t)tuning("STAGE2_ZPB", 25); }
 
 }  // namespace fimex_amd

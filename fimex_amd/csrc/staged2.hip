@@ -237,11 +237,16 @@ void launch_shape(const Staged2Plan& s, const Staged2Args& a, dim3 grid, hipStre
 
 }  // namespace
 
+int staged2_float_launch_order(const fimex_amd_regrid_plan& plan, size_t nz)
+{
+    return launch_order_of(tuning("STAGE2_ORDER", plan.chunkXcd ? kChunkPerXcd : kTileMajor), true, nz, staged2_zpb());
+}
+
 void launch_staged2_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream)
 {
     const Staged2Plan& s = staged2_shape_of(plan);
     Staged2Args a = staged2_args(plan, s, d_in, d_out, 4, nz);
-    const dim3 grid = staged2_z_chunks(a, s, nz);
+    const dim3 grid = staged2_z_chunks(a, s, nz, plan.chunkXcd ? kChunkPerXcd : kTileMajor, true);
     a.flags |= (uint32_t)tuning("STAGE2_STORE", 0) << 3;  // STORE 1 plain, 2 nt, 4 sc0 nt (default: sc1 nt)
     switch (plan.kind) {
     case PlanKind::Nearest: launch_shape<1>(s, a, grid, stream); break;

@@ -60,6 +60,7 @@ struct Staged2Args {
     uint32_t nz;
     uint32_t zStart[kMaxZChunks + 1];  // slices [zStart[c], zStart[c + 1]) belong to z chunk c
     uint32_t nZChunks;    // > 0: flat grid, the z chunks of a tile are consecutive workgroups of one XCD; 0: z chunk = blockIdx.y
+    uint32_t chunkPerXcd;  // flat grid only.  1: the chunk-per-XCD order, `order` is chunk_xcd_order's table (chunk_xcd_workgroup)
     uint32_t slotChunks;  // 16-byte chunks of one slot of the slice ring (a multiple of 64: whole wave instructions)
     uint32_t flags;      // tuning build only: 1 no source loads, 2 no result stores (STAGE2_ABLATE); the float kernel's store policy from 8 on
 };
@@ -92,11 +93,13 @@ inline Staged2Args staged2_args(const fimex_amd_regrid_plan& plan, const Staged2
     return a;
 }
 
-// the z chunks of a launch into the kernels' argument; flat: the grid is one-dimensional (flat_workgroup, staged_layout.hpp)
+// the z chunks of a launch into the kernels' argument; flat: the grid is one-dimensional, in tile-major order (flat_workgroup,
+// staged_layout.hpp) until the launcher says otherwise
 inline void set_z_chunks(Staged2Args& a, const ZChunks& zc, bool flat)
 {
     std::copy(zc.zStart, zc.zStart + kMaxZChunks + 1, a.zStart);
     a.nZChunks = flat ? zc.n : 0u;
+    a.chunkPerXcd = 0;
 }
 
 // the workgroup shape a float launch runs: the plan's choice (fimex_amd_regrid_plan_tune_device), or STAGE2_USE_ALT 0 / 1 in the
@@ -109,21 +112,33 @@ inline const Staged2Plan& staged2_shape_of(const fimex_amd_regrid_plan& plan)
 }
 
 // The z chunks of a float launch of nz slices (or pairs of slices) through shape `s`, written into `a`; returns the grid.
-// Tile-major order (the default, STAGE2_ORDER 1): the chunks of a tile are consecutive workgroups of one XCD, so
+// `order` is the plan's LaunchOrder (staged_layout.hpp), STAGE2_ORDER 0 / 1 / 2 replaces it in the tuning build.
+// Tile-major order (the default, 1): the chunks of a tile are consecutive workgroups of one XCD, so
 // they start together and fetch the tile's per-output plan -- 12 bytes per cell, 0.05 GB per chunk of the benchmark
 // launch -- once from memory instead of once per chunk, and the chip as a whole works on eight neighbouring tile rows;
 // chunks of one size (about STAGE2_ZPB slices).  Measured on the benchmark plan (round 2's sweeps, profiles/LAB_NOTES_r01_r02.md): bilinear
 // 2.40 -> 2.32 ms, nearest 2.32 -> 2.21 ms, 25 slices 0.322 -> 0.303 ms.
-// Chunk-major order (STAGE2_ORDER 0, round 1 and early round 2): all tiles of chunk 0, then chunk 1, ...; the chunks shrink
+// Chunk-per-XCD order (2): the transpose -- XCD x runs z chunk x of every tile, through `s.orderChunkXcd`.  The chip works on the
+// same 32 tiles x 8 chunks at any time, but a source line that two tiles need (nearly always vertical neighbours) is asked for
+// twice in ONE L2 instead of in two; the per-output plan is fetched by every XCD.  Needs 8 or 16 chunks: batches too short for
+// that (chunk_xcd_chunk_count) and launches with allowChunkPerXcd == false run tile-major.
+// Chunk-major order (0, round 1 and early round 2): all tiles of chunk 0, then chunk 1, ...; the chunks shrink
 // towards the end of the launch so that the last workgroups are short ones (STAGE2_ZTAIL).  The rules: float_z_chunks.
-inline dim3 staged2_z_chunks(Staged2Args& a, const Staged2Plan& s, size_t nz)
+inline dim3 staged2_z_chunks(Staged2Args& a, const Staged2Plan& s, size_t nz, int order, bool allowChunkPerXcd)
 {
-    const bool tileMajor = tuning("STAGE2_ORDER", 1) == 1;
-    const uint32_t zpb = (uint32_t)tuning("STAGE2_ZPB", tileMajor ? 25 : 50);
+    order = tuning("STAGE2_ORDER", order);
+    const bool tileMajor = order != kChunkMajor;
+    const uint32_t zpb = tileMajor ? staged2_zpb() : (uint32_t)tuning("STAGE2_ZPB", 50);
     const uint32_t ztail = tileMajor ? 0u : (uint32_t)tuning("STAGE2_ZTAIL", 10);  // 0: chunks of one size
+    order = launch_order_of(order, allowChunkPerXcd, nz, zpb);  // (staged2_float_launch_order, staged2.hip, answers the same)
     ZChunks zc;
-    FA_REQUIRE(float_z_chunks(nz, tileMajor, zpb, ztail, zc), "too many z chunks for one launch");
+    FA_REQUIRE(float_z_chunks(nz, order, zpb, ztail, zc), "too many z chunks for one launch");
     set_z_chunks(a, zc, tileMajor);
+    if (order == kChunkPerXcd) {
+        a.chunkPerXcd = 1;
+        a.order = s.orderChunkXcd.get();
+        return dim3(s.nTiles * zc.n, 1, 1);
+    }
     return dim3(tileMajor ? s.gridX * zc.n : s.gridX, tileMajor ? 1u : zc.n, 1);
 }
 

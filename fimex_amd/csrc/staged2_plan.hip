@@ -13,7 +13,8 @@
 //   * the plan stores the source offset of every 16-byte chunk of a tile, so the workgroup prologue is a coalesced load
 //     instead of a binary search per chunk, and row segments start on 16-byte boundaries of the slice for any row length
 //     (inX % 4 != 0 included: a reduced domain, src/CachedInterpolation.cc:159-200, crops to arbitrary widths);
-//   * tile rows are dealt to the XCDs in stripes (neighbours in x share an L2) through a workgroup -> tile table.
+//   * tile rows are dealt to the XCDs in stripes (neighbours in x share an L2) through a workgroup -> tile table; a second table
+//     holds the tiles in the sequence every XCD walks when the XCDs own z chunks instead (chunk_xcd_order, staged_layout.hpp).
 #include "staged2.hpp"
 #include "staged_common.hpp"
 
@@ -132,6 +133,11 @@ bool build_shape(const fimex_amd_regrid_plan& plan, Staged2Plan& s, const NeedSo
     const std::vector<uint32_t> order = xcd_order(bandOf, nBands, stripe);  // workgroup -> tile
     s.order.allocate(order.size());
     FA_HIP(hipMemcpyAsync(s.order.get(), order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    // and the table of the chunk-per-XCD order: cohorts of 8 bands x 4 tiles (STAGE2_COHORT_BANDS / _TILES), one XCD's 32 CUs
+    const std::vector<uint32_t> orderCx = chunk_xcd_order(tiles, bandOf, sh.tileW, (uint32_t)std::max(1, tuning("STAGE2_COHORT_BANDS", 8)),
+                                                          (uint32_t)std::max(1, tuning("STAGE2_COHORT_TILES", 4)));
+    s.orderChunkXcd.allocate(orderCx.size());
+    FA_HIP(hipMemcpyAsync(s.orderChunkXcd.get(), orderCx.data(), orderCx.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     FA_HIP(hipStreamSynchronize(stream));
     s.tiles = std::move(dTiles);
     s.nt = (uint32_t)sh.nt;

@@ -17,7 +17,7 @@ namespace {
 __device__ __forceinline__ bool decode_workgroup(const Staged2Args& a, StagedTile& T, uint32_t& z0, uint32_t& z1)
 {
     uint32_t slot0 = blockIdx.x, zc = blockIdx.y;
-    if (a.nZChunks != 0) flat_workgroup(blockIdx.x, a.nZChunks, slot0, zc);
+    if (a.nZChunks != 0) flat_grid_workgroup(blockIdx.x, a.nZChunks, a.chunkPerXcd, slot0, zc);
     const uint32_t tile = a.order[slot0];
     if (tile == 0xFFFFFFFFu) return false;
     T = a.tiles[tile];

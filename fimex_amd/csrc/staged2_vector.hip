@@ -205,7 +205,9 @@ void launch_staged2_apply_vector(const fimex_amd_regrid_plan& plan, const fimex_
     FA_REQUIRE(nz <= 0xFFFFFFFFu, "too many slices");
     const Staged2Plan& s = staged2_shape_of(plan);
     Staged2VectorArgs va{staged2_args(plan, s, d_u, d_uOut, 4, nz), d_v, d_vOut, vec.cossin.get()};
-    const dim3 grid = staged2_z_chunks(va.a, s, nz);  // chunks of pairs
+    // chunks of pairs; the pair kernel keeps the tile-major order whatever the plan's float launches run (the chunk-per-XCD
+    // order has not been timed on pairs)
+    const dim3 grid = staged2_z_chunks(va.a, s, nz, kTileMajor, false);
     if (plan.kind == PlanKind::Nearest) launch_shape<1>(s, va, grid, stream);
     else launch_shape<2>(s, va, grid, stream);
     FA_HIP(hipGetLastError());

@@ -1,8 +1,8 @@
 // The launch layout of the two LDS-staged regrid forms (staged.hip, staged2*.hip), stated once: how a target is cut into tiles,
 // which XCD runs which tile, which slices a workgroup takes, and how a workgroup finds its tile and z chunk again.  Plain
 // arithmetic without a HIP include: the plan builders and launchers call it on the host, the apply kernels call the decoders on
-// the device, and tests/test_staged_layout.py compiles it with g++ and checks on the CPU what no parity test shows -- that every
-// tile is computed, and computed once.
+// the device, and tests/test_staged_layout.py (the chunk-per-XCD order: tests/test_staged_layout_chunk_xcd.py) compiles it with g++
+// and checks on the CPU what no parity test shows -- that every tile is computed, and computed once.
 #pragma once
 
 #include <algorithm>
@@ -172,7 +172,61 @@ inline std::vector<uint32_t> xcd_order(const std::vector<uint32_t>& bandOf, uint
     return order;
 }
 
+// The table of the chunk-per-XCD order (chunk_xcd_workgroup below): XCD x runs z chunk x of EVERY tile, so all eight XCDs walk this
+// one sequence of tiles and nothing is padded.  The sequence is cut into cohorts of `by` bands x `bx` tiles, as many workgroups as
+// an XCD starts together, y fastest inside a cohort: vertical neighbours, which share most source lines (the target rows are
+// tilted against the source rows), are adjacent entries and meet in the XCD's L2.  The rule, for bands of unequal tile counts:
+//   band group   by consecutive bands;
+//   column       of a tile: where its middle lies in units of the widest tile, (x0 + w / 2) / tileW;
+//   cohort       the tiles of a band group in bx consecutive columns, in the order (column, band, x0); narrower tiles put more
+//                than by * bx tiles there: the cohort is then cut after by * bx of them and the rest is a cohort of its own, so
+//                that two tiles of one cohort are never more than by * bx - 1 entries apart.
+// Cohorts follow each other column group by column group, band group after band group.  cohortOf (optional): the cohort of
+// every entry of the result.
+inline std::vector<uint32_t> chunk_xcd_order(const std::vector<StagedTile>& tiles, const std::vector<uint32_t>& bandOf, uint32_t tileW,
+                                             uint32_t by, uint32_t bx, std::vector<uint32_t>* cohortOf = nullptr)
+{
+    by = std::max(by, 1u);
+    bx = std::max(bx, 1u);
+    tileW = std::max(tileW, 1u);
+    struct Key {
+        uint32_t group, columns, column, band, x0, tile;
+    };
+    std::vector<Key> keys(tiles.size());
+    for (size_t i = 0; i < tiles.size(); ++i) {
+        const uint32_t column = (tiles[i].x0 + tiles[i].w / 2) / tileW;
+        keys[i] = Key{bandOf[i] / by, column / bx, column, bandOf[i], tiles[i].x0, (uint32_t)i};
+    }
+    std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+        if (a.group != b.group) return a.group < b.group;
+        if (a.columns != b.columns) return a.columns < b.columns;
+        if (a.column != b.column) return a.column < b.column;
+        if (a.band != b.band) return a.band < b.band;
+        return a.x0 < b.x0;
+    });
+    std::vector<uint32_t> order(keys.size());
+    if (cohortOf) cohortOf->assign(keys.size(), 0);
+    uint32_t cohort = 0, held = 0;
+    for (size_t k = 0; k < keys.size(); ++k) {
+        if (k > 0 && (keys[k].group != keys[k - 1].group || keys[k].columns != keys[k - 1].columns || held == by * bx)) {
+            ++cohort;
+            held = 0;
+        }
+        ++held;
+        order[k] = keys[k].tile;
+        if (cohortOf) (*cohortOf)[k] = cohort;
+    }
+    return order;
+}
+
 // ---- z chunks
+
+// The order of a float launch of the second form (STAGE2_ORDER in the tuning build): which workgroup runs which tile and z chunk.
+enum LaunchOrder : int {
+    kChunkMajor = 0,   // two-dimensional grid: blockIdx.x -> xcd_order's table, blockIdx.y = z chunk
+    kTileMajor = 1,    // flat_workgroup: an XCD owns whole tiles, the z chunks of a tile are consecutive workgroups of it
+    kChunkPerXcd = 2,  // chunk_xcd_workgroup: an XCD owns z chunks, every XCD walks the same sequence of tiles
+};
 
 // slices [zStart[c], zStart[c + 1]) belong to z chunk c of n
 struct ZChunks {
@@ -193,13 +247,39 @@ inline ZChunks even_z_split(size_t nz, uint32_t n)
     return zc;
 }
 
-// The z chunks of a float launch of the second form, nz slices in chunks of about zpb.
-// Tile-major order: at most 16 chunks of one size.  Chunk-major order (all tiles of chunk 0, then chunk 1, ...): at most
-// kMaxZChunks - 6 before the tail; with ztail > 0 the chunks shrink towards the end of the launch so that the last workgroups are
-// short ones (the last 2 * zpb slices go in halves of at least ztail).  false: more than kMaxZChunks chunks.
-inline bool float_z_chunks(size_t nz, bool tileMajor, uint32_t zpb, uint32_t ztail, ZChunks& zc)
+// The chunk-per-XCD order needs a chunk count that is a multiple of the XCD count: 8 chunks, or 16 where the tile-major split of
+// the same batch makes more than 8, provided that no chunk gets shorter than (zpb + 1) / 2 slices -- the shortest chunk the
+// tile-major split makes of a batch longer than one chunk (zpb + 1 slices go in two).  0: the batch is too short, the launch
+// keeps the tile-major order and its chunks.
+inline uint32_t chunk_xcd_chunk_count(size_t nz, uint32_t zpb)
 {
     if (zpb < 1) zpb = 1;
+    if ((nz + zpb - 1) / zpb > 16) zpb = (uint32_t)((nz + 15) / 16);
+    const size_t shortest = (zpb + 1) / 2;
+    if ((nz + zpb - 1) / zpb > layout::kXcds && nz / (2 * layout::kXcds) >= shortest) return 2 * layout::kXcds;
+    return nz / layout::kXcds >= shortest ? layout::kXcds : 0u;
+}
+
+// The order a launch runs when `wanted` is asked for: the chunk-per-XCD order only where the launch allows it (the pair kernels do
+// not) and the batch is long enough, the tile-major order otherwise.
+inline int launch_order_of(int wanted, bool allowChunkPerXcd, size_t nz, uint32_t zpb)
+{
+    return wanted == kChunkPerXcd && !(allowChunkPerXcd && chunk_xcd_chunk_count(nz, zpb) != 0) ? (int)kTileMajor : wanted;
+}
+
+// The z chunks of a float launch of the second form, nz slices in chunks of about zpb, by launch order (LaunchOrder).
+// Tile-major order: at most 16 chunks of one size.  Chunk-per-XCD order: chunk_xcd_chunk_count chunks of one size, or the
+// tile-major split where that is 0.  Chunk-major order (all tiles of chunk 0, then chunk 1, ...): at most
+// kMaxZChunks - 6 before the tail; with ztail > 0 the chunks shrink towards the end of the launch so that the last workgroups are
+// short ones (the last 2 * zpb slices go in halves of at least ztail).  false: more than kMaxZChunks chunks.
+inline bool float_z_chunks(size_t nz, int order, uint32_t zpb, uint32_t ztail, ZChunks& zc)
+{
+    const bool tileMajor = order != kChunkMajor;
+    if (zpb < 1) zpb = 1;
+    if (order == kChunkPerXcd && chunk_xcd_chunk_count(nz, zpb) != 0) {
+        zc = even_z_split(nz, chunk_xcd_chunk_count(nz, zpb));
+        return true;
+    }
     const size_t mostChunks = tileMajor ? 16 : (size_t)kMaxZChunks - 6;
     if ((nz + zpb - 1) / zpb > mostChunks) zpb = (uint32_t)((nz + mostChunks - 1) / mostChunks);
     if (tileMajor) {
@@ -277,6 +357,25 @@ FA_LAYOUT_HD void flat_workgroup(uint32_t blockX, uint32_t nZChunks, uint32_t& s
     const uint32_t k = blockX / layout::kXcds;
     zc = k % nZChunks;
     slot = (k / nZChunks) * layout::kXcds + blockX % layout::kXcds;
+}
+
+// Flat grid of nTiles * n workgroups in chunk-per-XCD order, n a multiple of 8: workgroup s runs on XCD s % 8, and the k-th
+// workgroup of XCD x is z chunk x + 8 * (k % (n / 8)) of entry k / (n / 8) of chunk_xcd_order's table -- with 8 chunks workgroup s
+// is (entry s / 8, chunk s % 8); with 16 an XCD takes chunks x and x + 8 of an entry in turn.  The roles of the launch's three
+// carriers: blockIdx.x alone says XCD, entry and chunk; order[] (the same for every XCD) turns the entry into a tile, ~0u = none;
+// zStart[] turns the chunk into slices.
+FA_LAYOUT_HD void chunk_xcd_workgroup(uint32_t blockX, uint32_t nZChunks, uint32_t& slot, uint32_t& zc)
+{
+    const uint32_t k = blockX / layout::kXcds, perXcd = nZChunks / layout::kXcds;
+    slot = k / perXcd;
+    zc = blockX % layout::kXcds + (k % perXcd) * layout::kXcds;
+}
+
+// the decoder of a flat grid by the launch's mode (Staged2Args::chunkPerXcd)
+FA_LAYOUT_HD void flat_grid_workgroup(uint32_t blockX, uint32_t nZChunks, uint32_t chunkPerXcd, uint32_t& slot, uint32_t& zc)
+{
+    if (chunkPerXcd) chunk_xcd_workgroup(blockX, nZChunks, slot, zc);
+    else flat_workgroup(blockX, nZChunks, slot, zc);
 }
 
 }  // namespace fimex_amd

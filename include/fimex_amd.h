@@ -136,6 +136,7 @@ typedef struct fimex_amd_plan_info {
     size_t mappedSourceCells;  /* forward: source cells that fall inside the target grid */
     size_t stagedCells;        /* LDS-staged kernels (backward; forward plans with long buckets): source cells streamed per slice over all tiles (0: gather / lane kernels) */
     size_t tileW, tileH;       /* LDS-staged kernels: output cells per tile */
+    size_t launchOrder;        /* LDS-staged float launches of 104 slices and more: 0 an XCD runs whole tiles, 1 an XCD runs one z chunk of every tile (set by fimex_amd_regrid_plan_tune_device; same results).  The newest field: callers of fimex_amd_regrid_plan_info built before it existed must be rebuilt, the library fills the whole struct */
 } fimex_amd_plan_info;
 int fimex_amd_regrid_plan_info(const fimex_amd_regrid_plan* plan, fimex_amd_plan_info* info);
 
@@ -166,6 +167,16 @@ int fimex_amd_regrid_apply_device(const fimex_amd_regrid_plan* plan,
  */
 int fimex_amd_regrid_plan_tune_device(fimex_amd_regrid_plan* plan, const float* d_in, size_t nz, float* d_out, void* stream,
                                       int* chosenShape);
+
+/**
+ * The same call also chooses between two launch orders of the LDS-staged float kernels, again with identical results: an XCD
+ * (one of the chip's eight dies, each with its own L2) runs all z chunks of its tiles, the default, or one z chunk of every tile,
+ * which needs 8 or 16 z chunks and so a batch of at least 104 slices.  The second order is timed on the winning shape and kept by
+ * the same 1 % rule; fimex_amd_plan_info.launchOrder reports it.  This query answers for one batch length what
+ * fimex_amd_regrid_apply_device would launch: *order = 1 whole tiles per XCD, 2 z chunks per XCD, 0 the chunk-major order of the
+ * tuning build, -1 the batch does not run the LDS-staged float kernel of the second form.
+ */
+int fimex_amd_regrid_plan_launch_order(const fimex_amd_regrid_plan* plan, size_t nz, int* order);
 
 /**
  * Cross-check, no counterpart in the reference: the same regrid through the per-lane gather kernels (one lane per output cell

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """Runs scripts/sweep.py under rocprofv3 --pmc (one pass per counter group) and prints, per variant,
 kernel time and the L2 / fabric counters of the apply kernel.
-usage: python scripts/sweep_counters.py [--nz N] [--method M] variant...   (variants as for sweep.py)
+usage: python scripts/sweep_counters.py [--nz N] [--method M] [--json FILE] variant...   (variants as for sweep.py)
+--json FILE: the raw counter values per variant as well, with the bytes per launch in the form scripts/assemble_traffic.py reads.
 FETCH_SIZE is doubled (gfx950 tallies 128-B fabric reads at 64 B; calibrated with scripts/calib/calib.hip)."""
-import argparse, collections, csv, glob, os, subprocess, sys, shutil
+import argparse, collections, csv, glob, json, os, subprocess, sys, shutil
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GROUPS = [["FETCH_SIZE"], ["WRITE_SIZE"], ["TCC_REQ_sum", "TCC_MISS_sum", "TCC_HIT_sum"]]
 
@@ -12,6 +13,7 @@ def main():
     ap.add_argument("--nz", type=int, default=200)
     ap.add_argument("--method", default="bilinear")
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "sweepc"))
+    ap.add_argument("--json", default=None)
     ap.add_argument("variants", nargs="+")
     a = ap.parse_args()
     n = len(a.variants)
@@ -44,6 +46,13 @@ def main():
         print("%-34s %8.3f %9.2f %9.2f %9.1f %9.1f %7.1f" % (
             v or "(defaults)", r["ms_FETCH_SIZE"], 2 * r["FETCH_SIZE"] * 1024 / 1e9, r["WRITE_SIZE"] * 1024 / 1e9,
             r["TCC_REQ_sum"] / 1e6, r["TCC_MISS_sum"] / 1e6, 100 * r["TCC_HIT_sum"] / max(r["TCC_REQ_sum"], 1)), flush=True)
+    if a.json:
+        for r in res.values():  # FETCH_SIZE / WRITE_SIZE are in KiB
+            r["fetch_bytes_per_launch"], r["write_bytes_per_launch"] = 2 * r["FETCH_SIZE"] * 1024, r["WRITE_SIZE"] * 1024
+            r["hbm_bytes_per_launch"] = r["fetch_bytes_per_launch"] + r["write_bytes_per_launch"]
+        with open(a.json, "w") as f:
+            json.dump({"method": a.method, "nz": a.nz, "launches_counted": 1, "variants": res}, f, indent=1)
+            f.write("\n")
 
 if __name__ == "__main__":
     main()
