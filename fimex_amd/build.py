@@ -33,7 +33,7 @@ MERGE_VECTOR_MATH_SHIM = os.path.join(ROOT, "tests", "merge_vector_math_host.cc"
 MERGE_VECTOR_TYPED_MATH_LIB = os.path.join(HERE, "libmerge_vector_typed_math_host.so")  # csrc/merge_vector_typed_math.hpp compiled for the CPU with g++ (tests/test_merge_vector_typed_math_host.py)
 MERGE_VECTOR_TYPED_MATH_SHIM = os.path.join(ROOT, "tests", "merge_vector_typed_math_host.cc")
 
-DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_merge_typed.hip", "capi_merge_vector.hip", "capi_merge_vector_typed.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "staged2_vector_typed.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "merge_typed.hip", "merge_vector.hip", "merge_vector_typed.hip", "scaled_convert.hip", "pressure_convert.hip",
+DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_regrid_multi.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_merge_typed.hip", "capi_merge_vector.hip", "capi_merge_vector_typed.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "staged2_vector_typed.hip", "staged2_list.hip", "staged2_list_typed.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "merge_typed.hip", "merge_vector.hip", "merge_vector_typed.hip", "scaled_convert.hip", "pressure_convert.hip",
                   "time_accumulate.hip", "time_interpolate.hip", "quality.hip", "extract.hip", "vertical_plan.hip"]
 
 # -ffp-contract=off: the kernels reproduce the reference's IEEE arithmetic operation by operation
@@ -57,7 +57,7 @@ def _newer(target, deps):
 
 def _headers():
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")]
-    hdrs += [os.path.join(ROOT, "include", h) for h in ("fimex_amd.h", "fimex_amd_derived_host.h", "fimex_amd_time_quality_host.h", "fimex_amd_extract_host.h", "fimex_amd_vertical_plan_host.h", "fimex_amd_vector_regrid_host.h", "fimex_amd_vector_regrid_typed_host.h", "fimex_amd_merge_typed_host.h", "fimex_amd_merge_vector_host.h", "fimex_amd_merge_vector_typed_host.h")]
+    hdrs += [os.path.join(ROOT, "include", h) for h in ("fimex_amd.h", "fimex_amd_derived_host.h", "fimex_amd_time_quality_host.h", "fimex_amd_extract_host.h", "fimex_amd_vertical_plan_host.h", "fimex_amd_vector_regrid_host.h", "fimex_amd_vector_regrid_typed_host.h", "fimex_amd_merge_typed_host.h", "fimex_amd_merge_vector_host.h", "fimex_amd_merge_vector_typed_host.h", "fimex_amd_regrid_multi_host.h")]
     return hdrs
 
 

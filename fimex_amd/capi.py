@@ -146,6 +146,9 @@ SYMBOLS = {
     "fimex_amd_data2interpolation_device": (ctypes.c_int, [_V, ctypes.c_int, _Z, ctypes.c_double, _V, _V]),
     "fimex_amd_interpolation2data_device": (ctypes.c_int, [_V, _Z, ctypes.c_int, ctypes.c_double, _V, _V]),
     "fimex_amd_regrid_apply_typed_device": (ctypes.c_int, [_V, _V, ctypes.c_int, _Z, ctypes.c_double, _V, _V]),
+    "fimex_amd_regrid_apply_multi_device": (ctypes.c_int, [_V, _Z, ctypes.POINTER(_V), _ZP, ctypes.POINTER(_V), _V, ctypes.POINTER(ctypes.c_int)]),
+    "fimex_amd_regrid_apply_multi_typed_device": (ctypes.c_int, [_V, _Z, ctypes.POINTER(_V), ctypes.c_int, _ZP, _D, ctypes.POINTER(_V), _V,
+                                                                 ctypes.POINTER(ctypes.c_int)]),
     "fimex_amd_regrid_apply_vector_typed_device": (ctypes.c_int, [_V, _V, _V, ctypes.c_int, ctypes.c_double, _V, ctypes.c_int, ctypes.c_double, _Z,
                                                                   _V, _V, _V, ctypes.POINTER(ctypes.c_int)]),
     "fimex_amd_data2interpolation_host": (ctypes.c_int, [_V, ctypes.c_int, _Z, ctypes.c_double, _F]),
@@ -301,6 +304,14 @@ VERTICAL_PLAN_HOST_SYMBOLS = {
     "fimex_amd_vertical_plan_read_host": (ctypes.c_int, [_V, ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_uint), _F]),
 }
 
+# name -> (restype, argtypes); every symbol include/fimex_amd_regrid_multi_host.h declares: a list of variables regridded in one call, on host buffers
+REGRID_MULTI_HOST_SYMBOLS = {
+    "fimex_amd_regrid_apply_multi_host": (ctypes.c_int, [_V, _Z, ctypes.POINTER(_V), _ZP, ctypes.POINTER(_V), ctypes.POINTER(ctypes.c_int)]),
+    "fimex_amd_regrid_apply_multi_typed_host": (ctypes.c_int, [_V, _Z, ctypes.POINTER(_V), ctypes.c_int, _ZP, _D, ctypes.POINTER(_V),
+                                                               ctypes.POINTER(ctypes.c_int)]),
+}
+REGRID_MULTI_MAX_VARS = 64  # FIMEX_AMD_REGRID_MULTI_MAX_VARS
+
 _lib = None
 _libs = {}
 
@@ -318,7 +329,7 @@ def _open(path):
     for name, (res, args) in list(SYMBOLS.items()) + list(DERIVED_HOST_SYMBOLS.items()) + list(TIME_QUALITY_HOST_SYMBOLS.items()) + list(
             EXTRACT_HOST_SYMBOLS.items()) + list(VERTICAL_PLAN_HOST_SYMBOLS.items()) + list(VECTOR_REGRID_HOST_SYMBOLS.items()) + list(
             VECTOR_REGRID_TYPED_HOST_SYMBOLS.items()) + list(MERGE_TYPED_HOST_SYMBOLS.items()) + list(MERGE_VECTOR_HOST_SYMBOLS.items()) + list(
-            MERGE_VECTOR_TYPED_HOST_SYMBOLS.items()):
+            MERGE_VECTOR_TYPED_HOST_SYMBOLS.items()) + list(REGRID_MULTI_HOST_SYMBOLS.items()):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -435,6 +446,44 @@ class RegridPlan:
 
     def apply_device(self, d_in, nz, d_out, stream=0):
         _check(load().fimex_amd_regrid_apply_device(self._h, d_in, nz, d_out, stream))
+
+    def apply_multi_device(self, d_in, nz, d_out, stream=0, cdmType=None, badValue=None):
+        """A list of variables in one call: d_in / d_out sequences of device pointers, nz the slices of each.  cdmType None: float
+        slices; else the variables' stored type, badValue one fill value for all or one per variable.  Only enqueues on `stream`.
+        Returns the path: 1 the list kernels, 0 the per-variable calls."""
+        n = len(nz)
+        if len(d_in) != n or len(d_out) != n:
+            raise ValueError("as many inputs and outputs as slice counts")
+        ins, outs = (_V * max(n, 1))(*d_in), (_V * max(n, 1))(*d_out)
+        nzs = (_Z * max(n, 1))(*nz)
+        path = ctypes.c_int(-1)
+        if cdmType is None:
+            _check(load().fimex_amd_regrid_apply_multi_device(self._h, n, ins, nzs, outs, stream, ctypes.byref(path)))
+        else:
+            bad = np.ascontiguousarray(np.broadcast_to(np.asarray(float("nan") if badValue is None else badValue, dtype=np.float64), (n,)))
+            _check(load().fimex_amd_regrid_apply_multi_typed_device(self._h, n, ins, cdmType, nzs, _dp(bad), outs, stream, ctypes.byref(path)))
+        return path.value
+
+    def apply_multi_host(self, arrays, badValue=None):
+        """The same on host arrays [nz[i]][inY][inX] of one element type (float32, or a stored type with badValue as above); returns
+        (the regridded arrays [nz[i]][outY][outX], path)."""
+        arrs = [np.ascontiguousarray(a) for a in arrays]
+        n = len(arrs)
+        layer = self.inX * self.inY
+        nz = [a.size // layer for a in arrs]
+        dtype = arrs[0].dtype if n else np.dtype(np.float32)
+        if any(a.dtype != dtype or a.size != z * layer for a, z in zip(arrs, nz)):
+            raise ValueError("arrays of one element type, each a whole number of source slices")
+        outs = [np.empty((z, self.outY, self.outX), dtype=dtype) for z in nz]
+        ins_p, outs_p = (_V * max(n, 1))(*[a.ctypes.data for a in arrs]), (_V * max(n, 1))(*[o.ctypes.data for o in outs])
+        nzs = (_Z * max(n, 1))(*nz)
+        path = ctypes.c_int(-1)
+        if dtype == np.float32 and badValue is None:
+            _check(load().fimex_amd_regrid_apply_multi_host(self._h, n, ins_p, nzs, outs_p, ctypes.byref(path)))
+        else:
+            bad = np.ascontiguousarray(np.broadcast_to(np.asarray(float("nan") if badValue is None else badValue, dtype=np.float64), (n,)))
+            _check(load().fimex_amd_regrid_apply_multi_typed_host(self._h, n, ins_p, cdm_type_of(dtype), nzs, _dp(bad), outs_p, ctypes.byref(path)))
+        return outs, path.value
 
     def apply_vector_device(self, vec, d_u, d_v, nz, d_uOut, d_vOut, stream=0):
         """getDataSlice's vector branch on device buffers: both components regridded and rotated by `vec` (a VectorPlan on the

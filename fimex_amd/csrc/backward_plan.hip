@@ -6,6 +6,8 @@
 #include "plan.hpp"
 #include "stencil_math.hpp"
 
+#include "slice_list.hpp"
+
 namespace fimex_amd {
 
 namespace {
@@ -183,6 +185,67 @@ bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int
     // bicubic: the LDS-staged float kernel between two conversion passes beats a 16-load gather on the stored type
     if (plan.kind == PlanKind::Forward || (plan.kind == PlanKind::Bicubic && tuning("TYPED_FUSED", 1) < 2) || tuning("TYPED_FUSED", 1) == 0) return false;
     return launch_typed_gather(plan, d_in, cdmType, nz, badValue, d_out, stream);
+}
+
+namespace {
+
+// the slices of a list, 0 where there are more than a launch counts
+size_t list_slices(const size_t* nz, size_t nvar)
+{
+    size_t total = 0;
+    for (size_t i = 0; i < nvar; ++i) {
+        if (nz[i] > 0xFFFFFFFFu - total) return 0;
+        total += nz[i];
+    }
+    return total;
+}
+
+// launch(first, count) on runs of the list that hold at most kSliceListMaxVars variables with slices
+template <class Launch>
+void for_list_launches(const size_t* nz, size_t nvar, Launch&& launch)
+{
+    size_t first = 0, held = 0;
+    for (size_t i = 0; i < nvar; ++i) {
+        if (nz[i] == 0) continue;
+        if (held == kSliceListMaxVars) {
+            launch(first, i - first);
+            first = i;
+            held = 0;
+        }
+        ++held;
+    }
+    if (held) launch(first, nvar - first);
+}
+
+}  // namespace
+
+bool launch_backward_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
+                                hipStream_t stream)
+{
+    const size_t total = list_slices(nz, nvar);
+    if (plan.kind == PlanKind::Forward || !takes_second_form(plan, total) || !staged2_list_serves(plan)) return false;
+    for_list_launches(nz, nvar, [&](size_t first, size_t count) {
+        launch_staged2_apply_list(plan, count, d_in + first, nz + first, d_out + first, stream);
+    });
+    return true;
+}
+
+// (the switches and the batch length of launch_typed_apply's second staged form; the types, the plans and the alignment of
+// launch_staged2_apply_typed)
+bool launch_typed_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const void* const* d_in, int cdmType, const size_t* nz,
+                             const double* badValue, void* const* d_out, hipStream_t stream)
+{
+    const size_t total = list_slices(nz, nvar);
+    if (plan.kind == PlanKind::Forward || tuning("TYPED_FUSED", 1) == 0 || tuning("STAGED", 1) == 0 || tuning("TYPED_STAGED", 1) == 0 ||
+        tuning("TYPED_STAGED2", 1) == 0 || total < staged_min_nz())
+        return false;
+    for (size_t i = 0; i < nvar; ++i)
+        if (nz[i] != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % 4 != 0) return false;
+    if (!staged2_list_typed_serves(plan, cdmType, stream)) return false;
+    for_list_launches(nz, nvar, [&](size_t first, size_t count) {
+        launch_staged2_apply_list_typed(plan, count, d_in + first, cdmType, nz + first, badValue + first, d_out + first, stream);
+    });
+    return true;
 }
 
 }  // namespace fimex_amd

@@ -15,6 +15,19 @@ void apply_plan_device(const fimex_amd_regrid_plan& plan, const float* d_in, siz
     else launch_backward_apply(plan, d_in, nz, d_out, stream);
 }
 
+// on the stored type: one kernel where launch_typed_apply has one, the three passes on temporaries otherwise
+void apply_plan_typed_device(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+                             hipStream_t st)
+{
+    if (launch_typed_apply(plan, d_in, cdmType, nz, badValue, d_out, st)) return;
+    const size_t inLayer = plan.inX * plan.inY, outLayer = plan.outX * plan.outY;
+    DeviceArray<float> fIn(nz * inLayer), fOut(nz * outLayer);
+    launch_data2interpolation(d_in, cdmType, nz * inLayer, badValue, fIn.get(), st);
+    apply_plan_device(plan, fIn.get(), nz, fOut.get(), st);
+    launch_interpolation2data(fOut.get(), nz * outLayer, cdmType, badValue, d_out, st);
+    FA_HIP(hipStreamSynchronize(st));  // the temporaries are released on return
+}
+
 namespace {
 
 bool is_backward(int funcType)
@@ -486,14 +499,7 @@ int fimex_amd_regrid_apply_typed_device(const fimex_amd_regrid_plan* plan, const
         if (nz == 0) return;
         FA_REQUIRE(d_in != nullptr && d_out != nullptr, "NULL device buffer");
         ScopedDevice dev(plan->device);
-        hipStream_t st = as_stream(stream);
-        if (launch_typed_apply(*plan, d_in, cdmType, nz, badValue, d_out, st)) return;
-        const size_t inLayer = plan->inX * plan->inY, outLayer = plan->outX * plan->outY;
-        DeviceArray<float> fIn(nz * inLayer), fOut(nz * outLayer);
-        launch_data2interpolation(d_in, cdmType, nz * inLayer, badValue, fIn.get(), st);
-        apply_plan_device(*plan, fIn.get(), nz, fOut.get(), st);
-        launch_interpolation2data(fOut.get(), nz * outLayer, cdmType, badValue, d_out, st);
-        FA_HIP(hipStreamSynchronize(st));  // the temporaries are released on return
+        apply_plan_typed_device(*plan, d_in, cdmType, nz, badValue, d_out, as_stream(stream));
     });
 }
 

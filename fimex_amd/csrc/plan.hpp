@@ -157,6 +157,14 @@ void launch_backward_apply(const fimex_amd_regrid_plan& plan, const float* d_in,
 int backward_launch_order(const fimex_amd_regrid_plan& plan, size_t nz);
 bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                         hipStream_t stream);
+// A list of variables, variable i an array of nz[i] slices of its own, through the second staged form's list kernels
+// (staged2_list.hip, staged2_list_typed.hip) in launches of at most kSliceListMaxVars variables.  false, and nothing launched: the
+// slices together are no batch of the second staged form (the rule of launch_backward_apply / launch_typed_apply on the SUM of
+// nz[]), or a source of a stored type is not 4-byte aligned; the caller runs the variables one by one.
+bool launch_backward_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
+                                hipStream_t stream);
+bool launch_typed_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const void* const* d_in, int cdmType, const size_t* nz,
+                             const double* badValue, void* const* d_out, hipStream_t stream);
 // gather.hip: the per-lane gather kernel on float slices and on stored types
 void launch_backward_gather(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
 bool launch_typed_gather(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
@@ -173,6 +181,14 @@ bool build_staged2_plan(fimex_amd_regrid_plan& plan, const double* d_px, const d
 // staged2.hip
 void launch_staged2_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
 int staged2_float_launch_order(const fimex_amd_regrid_plan& plan, size_t nz);  // the LaunchOrder launch_staged2_apply runs nz slices in
+// staged2_list.hip, staged2_list_typed.hip: one launch on the slices of nvar <= kSliceListMaxVars variables; `serves`: the list
+// kernels exist for the workgroup shape the plan's launches run (and, stored types, the plan has a form for the type)
+bool staged2_list_serves(const fimex_amd_regrid_plan& plan);
+void launch_staged2_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
+                               hipStream_t stream);
+bool staged2_list_typed_serves(const fimex_amd_regrid_plan& plan, int cdmType, hipStream_t stream);
+void launch_staged2_apply_list_typed(const fimex_amd_regrid_plan& plan, size_t nvar, const void* const* d_in, int cdmType, const size_t* nz,
+                                     const double* badValue, void* const* d_out, hipStream_t stream);
 // staged2_vector.hip: both components of a vector pair regridded and rotated in one launch; `serves` is the dispatch rule
 // (nearest / bilinear plans with the second staged form, batches of staged_min_nz() pairs and more, VECTOR_FUSED not 0)
 bool staged2_vector_serves(const fimex_amd_regrid_plan& plan, size_t nz);
@@ -371,6 +387,8 @@ fimex_amd_batch* batch_alloc_source(const fimex_amd_regrid_plan& plan, size_t nz
 void batch_free(fimex_amd_batch* batch);
 const fimex_amd_batch_info& batch_info(const fimex_amd_batch& batch);
 void apply_plan_device(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
+void apply_plan_typed_device(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+                             hipStream_t stream);
 // capi_vector.hip: a vector pair regridded and rotated as fimex_amd_regrid_apply_vector_device serves it; returns the path taken
 int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
                       float* d_uOut, float* d_vOut, hipStream_t stream);

@@ -8,6 +8,8 @@
 #include "staged2.hpp"
 #include "staged_common.hpp"
 
+#include "slice_list.hpp"  // (behind the HIP headers: its functions are host and device functions here)
+
 #include <type_traits>
 
 namespace fimex_amd {
@@ -55,11 +57,71 @@ __device__ __forceinline__ void dispatch_un(uint32_t un, bool plainWave, Body&& 
     }
 }
 
+// ---- which memory a slice of the launch is: the ring's policy
+
+// The array form, the default: slice z of the launch is slice z of one source array and of one result array, base + z * bytes.
+// No state and no code of its own.
+struct ArraySlices {
+    static constexpr bool kList = false;
+};
+
+// what a list launch (staged2_list.hip, staged2_list_typed.hip) knows of its variables, in the kernel arguments
+struct SliceListArgs {
+    SliceEnds e;
+    uint64_t exactMask;  // bit k: variable k is computed in the reference's arithmetic (see SliceRing::exact_slice)
+    const char* in[kSliceListMaxVars];
+    char* out[kSliceListMaxVars];
+};
+
+// The list form: logical slice l of the launch is a level of one of up to kSliceListMaxVars variables, each an array of its own
+// (slice_list.hpp).  The ring fetches slice z + DEPTH - 1 while slice z is interpolated and stored, so a workgroup holds two
+// cursors: `src`, the next slice to fetch, runs ahead; `cur` is the slice in work -- its result, and its source for the loops that
+// read memory directly.  Both are seeded at the chunk's z0 and moved one slice at a time: `src` by every fetch, `cur` by
+// slice_done().  Scalar and wave-uniform, said explicitly as uniform() does for the pointers.
+struct ListSlices {
+    static constexpr bool kList = true;
+    const SliceListArgs* list;
+    mutable SliceCursor src, cur;  // (moved by the const ring's loop)
+
+    __device__ __forceinline__ static void make_uniform(SliceCursor& c)
+    {
+        c.var = __builtin_amdgcn_readfirstlane(c.var);
+        c.level = __builtin_amdgcn_readfirstlane(c.level);
+        c.left = __builtin_amdgcn_readfirstlane(c.left);
+    }
+    __device__ __forceinline__ void seed(const SliceListArgs* l, uint32_t z0)
+    {
+        list = l;
+        cur = slice_seek(l->e.ends, l->e.nvar, z0);
+        make_uniform(cur);
+        src = cur;
+    }
+    __device__ __forceinline__ static void step(const SliceListArgs* l, SliceCursor& c)
+    {
+        slice_advance(l->e.ends, l->e.nvar, c);
+        make_uniform(c);
+    }
+    __device__ __forceinline__ const char* fetch(uint32_t inBytes) const
+    {
+        const char* p = uniform(list->in[src.var] + (size_t)src.level * inBytes);
+        step(list, src);
+        return p;
+    }
+    __device__ __forceinline__ const char* in_cur(uint32_t inBytes) const { return uniform(list->in[cur.var] + (size_t)cur.level * inBytes); }
+    __device__ __forceinline__ char* out_cur(uint32_t outBytes) const
+    {
+        return const_cast<char*>(uniform(list->out[cur.var] + (size_t)cur.level * outBytes));
+    }
+};
+
 // The slice ring of one workgroup of NT threads, in its dynamic LDS: DEPTH slots, each holds the largest tile of the plan, then 1 KiB that is never
 // read.  Construction loads the lane's staging list and issues the DMAs of the first DEPTH - 1 slices, so it comes before
 // everything else in a kernel: the per-output plan loads while they fly.
-template <int NT, int KMAX, int DEPTH>
-struct SliceRing {
+// Slices: where slice z lies.  Array form: in(z) / out(z).  List form: the ring asks for the slices of its chunk in order, each
+// once -- source(z) moves the source cursor, and whoever walks the slices says slice_done() after each (run() does; the kernels'
+// loops that do not go through the ring do it themselves); z only counts.
+template <int NT, int KMAX, int DEPTH, class Slices = ArraySlices>
+struct SliceRing : Slices {
     const char* inBase;
     char* outBase;
     uint32_t inBytes, outBytes;      // one source / result slice
@@ -93,7 +155,8 @@ struct SliceRing {
         }
     }
 
-    __device__ __forceinline__ SliceRing(const Staged2Args& a, const StagedTile& T, uint32_t z0_, uint32_t z1_, uint32_t elemBytes)
+    __device__ __forceinline__ SliceRing(const Staged2Args& a, const StagedTile& T, uint32_t z0_, uint32_t z1_, uint32_t elemBytes,
+                                         const SliceListArgs* list = nullptr)
         : inBase(reinterpret_cast<const char*>(a.in)), outBase(reinterpret_cast<char*>(a.out)), inBytes(a.inBytes),
           outBytes(a.nOut * elemBytes), inRecords((kTuningBuild && (a.flags & 1)) ? 0u : a.inBytes),
           outRecords((kTuningBuild && (a.flags & 2)) ? 0u : a.nOut * elemBytes), z0(z0_), z1(z1_), un((T.nChunks + NT - 1) / NT),
@@ -104,24 +167,66 @@ struct SliceRing {
             const uint32_t c = threadIdx.x + j * NT;
             gOff[j] = (c < T.nChunks) ? a.chunkOff[T.chunkBase + c] * elemBytes : 0xFFFFFFFFu;  // ~0u: dropped by the bounds check (zeros)
         }
+        if constexpr (Slices::kList) this->seed(list, z0);
         for (uint32_t i = 0; i + 1 < (uint32_t)DEPTH && i < z1 - z0; ++i) {
-            const rsrc_t rs = in(z0 + i);
+            const rsrc_t rs = source(z0 + i);
 #pragma unroll
             for (int j = 0; j < KMAX; ++j)
                 if ((uint32_t)j < un) dma16(rs, dma_dst(i, j), gOff[j]);
         }
     }
 
-    __device__ __forceinline__ rsrc_t in(uint32_t z) const { return make_rsrc(inBase + (size_t)z * inBytes, inRecords); }
-    __device__ __forceinline__ rsrc_t out(uint32_t z) const { return make_rsrc(outBase + (size_t)z * outBytes, outRecords); }
+    __device__ __forceinline__ rsrc_t in(uint32_t z) const
+    {
+        static_assert(!Slices::kList, "a list has no slice z of one array: source(z), in_uniform(z)");
+        return make_rsrc(inBase + (size_t)z * inBytes, inRecords);
+    }
+    // the source of the next slice to fetch, z: every buffer resource is one slice, with the slice's own size
+    __device__ __forceinline__ rsrc_t source(uint32_t z) const
+    {
+        if constexpr (Slices::kList) return make_rsrc(this->fetch(inBytes), inRecords);
+        else return in(z);
+    }
+    __device__ __forceinline__ rsrc_t out(uint32_t z) const
+    {
+        if constexpr (Slices::kList) return make_rsrc(this->out_cur(outBytes), outRecords);
+        else return make_rsrc(outBase + (size_t)z * outBytes, outRecords);
+    }
+    // the slice in work is finished, the next one follows
+    __device__ __forceinline__ void slice_done() const
+    {
+        if constexpr (Slices::kList) Slices::step(this->list, this->cur);
+    }
+    // List form, FIMEX_AMD_BICUBIC_FAST plans: whether the slice in work is computed in the reference's arithmetic after all.  A
+    // variable of fewer than staged_min_nz() slices, called on its own, runs the gather kernel, which knows no other arithmetic;
+    // in a list it gets the same bytes.
+    __device__ __forceinline__ bool exact_slice() const
+    {
+        if constexpr (Slices::kList) return ((this->list->exactMask >> this->cur.var) & 1u) != 0;
+        else return false;
+    }
+    // list form: the variable of the slice in work (stored types: its fill value)
+    __device__ __forceinline__ uint32_t variable() const
+    {
+        if constexpr (Slices::kList) return this->cur.var;
+        else return 0u;
+    }
     // logical slice l of a pair ring
     __device__ __forceinline__ rsrc_t in_pair(uint32_t l) const
     {
         return make_rsrc(((l & 1u) ? inBaseV : inBase) + (size_t)(z0 + l / 2u) * inBytes, inRecords);
     }
     // for the loops that do not go through the ring (gather tiles)
-    __device__ __forceinline__ rsrc_t in_uniform(uint32_t z) const { return make_rsrc(uniform(inBase + (size_t)z * inBytes), inRecords); }
-    __device__ __forceinline__ rsrc_t out_uniform(uint32_t z) const { return make_rsrc(uniform(outBase + (size_t)z * outBytes), outRecords); }
+    __device__ __forceinline__ rsrc_t in_uniform(uint32_t z) const
+    {
+        if constexpr (Slices::kList) return make_rsrc(this->in_cur(inBytes), inRecords);
+        else return make_rsrc(uniform(inBase + (size_t)z * inBytes), inRecords);
+    }
+    __device__ __forceinline__ rsrc_t out_uniform(uint32_t z) const
+    {
+        if constexpr (Slices::kList) return out(z);
+        else return make_rsrc(uniform(outBase + (size_t)z * outBytes), outRecords);
+    }
 
     // A lane without a chunk carries an offset beyond the slice and the DMA writes ZEROS for it (scripts/calib/dma_oob.hip):
     // inside the slot that is unused space, but a slot is not a whole number of NT chunks, and the last wave instructions of a
@@ -157,11 +262,12 @@ struct SliceRing {
             const bool more = i + DEPTH - 1 < nzl;
             if (more) {  // into the slot slice i - 1 has left
                 const uint32_t sl = (slot + DEPTH - 1 >= (uint32_t)DEPTH) ? slot - 1 : slot + DEPTH - 1;
-                const rsrc_t rs = in(z + DEPTH - 1);
+                const rsrc_t rs = source(z + DEPTH - 1);
 #pragma unroll
                 for (int j = 0; j < UN; ++j) dma16(rs, dma_dst(sl, j), gOff[j]);
             }
             sliceBody(z, reinterpret_cast<const char*>(smem + slot * slotFloats));
+            slice_done();
             if (more) wait_vmcnt<(DEPTH - 2) * UN + (DEPTH - 1) * STORES>();
             else wait_vmcnt<STORES>();  // the tail of the z chunk: everything but this slice's stores
             __builtin_amdgcn_s_barrier();

@@ -1,171 +1,23 @@
 // The second LDS-staged regrid form (staged2.hip) on a variable's STORED type: kernel, form cache and launch (data2InterpolationArray + interpolateValues +
 // interpolationArray2Data of src/CDMInterpolator.cc:115-124, 251-285 in one kernel): slices of 1- or 2-byte integers.
 // The plan form is its own (built on first use, staged2_typed_form): a 16-byte chunk holds 8 or 16 source cells, LDS offsets
-// count elements.  Differences to the float kernel: a lane owns two PAIRS of neighbouring outputs (cells 2 * t, 2 * t + 1 of
-// the tile, and the same NT * 2 cells further on), so that two results leave in one 4-byte (2-byte elements) or 2-byte store
-// and a wave still writes 256 (128) contiguous bytes; the two source elements of a stencil row arrive in one ds_read2_b32 and
-// are shifted apart; elements become float / NaN as Data::asFloat + mifi_bad2nanf do, results go back through ScaleValue's
-// rounding (typed_convert.hpp); the element reads and the stores are staged2_lane_ops.hpp's.
-#include "staged2_lane_ops.hpp"
-#include "staged2_ring.hpp"
+// count elements.  The kernel's text: staged2_apply_typed_kernel.hpp; how it differs from the float kernel: staged2_apply_typed.hpp.
+#include "staged2_apply_typed.hpp"
+
+// the kernel on the slices of one array
+#define STAGED2_KERNEL staged_apply2_typed
+#define STAGED2_SLICES ArraySlices
+#define STAGED2_LIST_PARAM
+#define STAGED2_LIST nullptr
+#define STAGED2_EDGES static_cast<const TypedListEdge*>(nullptr)
+#include "staged2_apply_typed_kernel.hpp"
+#undef STAGED2_KERNEL
+#undef STAGED2_SLICES
+#undef STAGED2_LIST_PARAM
+#undef STAGED2_LIST
+#undef STAGED2_EDGES
 
 namespace fimex_amd {
-
-namespace {
-
-struct TypedEdge {
-    float bad;          // the variable's fill value narrowed to float (mifi_bad2nanf's argument)
-    uint32_t hasBad;
-    double fillOut;     // NaN -> this (interpolationArray2Data)
-    uint32_t pairStore; // outX even: the two results of a pair share one store
-};
-
-// STENCIL 1 (nearest) or 2 (bilinear); NT threads, 4 outputs per lane (two pairs); KMAX 16-byte chunks per lane and slice
-// PAIR: the row length and the slice start allow aligned stores of two results
-template <int STENCIL, int NT, int KMAX, typename T, bool PAIR, int DEPTH = 2>
-__global__ void __launch_bounds__(NT) staged_apply2_typed(Staged2Args a, TypedEdge te)
-{
-    static_assert(STENCIL == 1 || STENCIL == 2, "stored types: nearest and bilinear");
-    constexpr uint32_t EB = sizeof(T);
-    constexpr int PER = 4;
-    StagedTile T_;
-    uint32_t z0, z1;
-    if (!decode_workgroup(a, T_, z0, z1)) return;
-    const SliceRing<NT, KMAX, DEPTH> ring(a, T_, z0, z1, EB);
-    const bool hasBad = te.hasBad != 0;
-    const T fillT = static_cast<T>(te.fillOut);  // ScaleValue's newFill_ (include/fimex/Utils.h:456)
-    // per-lane plan: output q = 2 * p + h is cell 2 * threadIdx.x + h + p * 2 * NT of the tile (row-major over the tile's width)
-    uint32_t cellOff[PER];       // byte offset inside a typed output slice, ~0u = not mine
-    uint32_t row[PER][STENCIL];  // byte offsets of the stencil rows in the staged image
-    uint32_t cellIdx[PER];
-    float xf[PER], yf[PER];
-    bool undef[PER];
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        const uint32_t e = 2u * threadIdx.x + (uint32_t)(q & 1) + (uint32_t)(q >> 1) * 2u * NT;
-        const uint32_t ly = e / T_.w, lx = e - ly * T_.w;
-        const uint32_t y = T_.y0 + ly;
-        cellOff[q] = 0xFFFFFFFFu;
-        cellIdx[q] = 0xFFFFFFFFu;
-        uint32_t pa = kInvalidPos;
-        xf[q] = yf[q] = 0.f;
-        if (ly < a.tileH && y < a.outY) {
-            const uint32_t cell = y * a.outX + T_.x0 + lx;
-            cellIdx[q] = cell;
-            cellOff[q] = cell * EB;
-            pa = a.ldsA[cell];
-            if (STENCIL == 2) { xf[q] = a.xf[cell]; yf[q] = a.yf[cell]; }
-        }
-        undef[q] = pa == kInvalidPos;
-        row[q][0] = undef[q] ? 0u : (pa & 0xFFFFu) * EB;
-        if (STENCIL == 2) row[q][STENCIL - 1] = undef[q] ? 0u : (pa >> 16) * EB;
-    }
-    if (T_.rsv[0] != 0) {
-        // gather tile (see staged_apply2): stencils straight from memory, element by element
-        uint32_t p[PER];
-#pragma unroll
-        for (int q = 0; q < PER; ++q) {
-            p[q] = (cellIdx[q] != 0xFFFFFFFFu) ? a.pos[cellIdx[q]] : kInvalidPos;
-            undef[q] = p[q] == kInvalidPos;
-            if (undef[q]) p[q] = 0;
-        }
-        for (uint32_t z = z0; z < z1; ++z) {
-            const rsrc_t rs = ring.in_uniform(z), ro = ring.out_uniform(z);
-            auto ld = [&](uint32_t cell) {
-                if constexpr (EB == 2) return as_float_nan((T)__builtin_amdgcn_raw_buffer_load_b16(rs, cell * 2u, 0, 0), te.bad, hasBad);
-                else return as_float_nan((T)__builtin_amdgcn_raw_buffer_load_b8(rs, cell, 0, 0), te.bad, hasBad);
-            };
-            float r[PER];
-#pragma unroll
-            for (int q = 0; q < PER; ++q) {
-                if constexpr (STENCIL == 1) {
-                    r[q] = ld(p[q]);
-                } else {
-                    const uint32_t dx = is_nn(xf[q]) ? 0u : 1u, dy = is_nn(yf[q]) ? 0u : a.inX;
-                    r[q] = bilinear_value(ld(p[q]), ld(p[q] + dx), ld(p[q] + dy), ld(p[q] + dx + dy), xf[q], yf[q]);
-                }
-                if (undef[q]) r[q] = undefined_f();
-            }
-            store_pair<T, PAIR>(ro, cellOff[0], cellOff[1], r[0], r[1], fillT);
-            store_pair<T, PAIR>(ro, cellOff[2], cellOff[3], r[2], r[3], fillT);
-        }
-        return;
-    }
-    if (T_.nChunks == 0) {  // every output of the tile is undefined
-        for (uint32_t z = z0; z < z1; ++z) {
-            const rsrc_t ro = ring.out(z);
-            store_pair<T, PAIR>(ro, cellOff[0], cellOff[1], undefined_f(), undefined_f(), fillT);
-            store_pair<T, PAIR>(ro, cellOff[2], cellOff[3], undefined_f(), undefined_f(), fillT);
-        }
-        return;
-    }
-    ring.wait_first();
-    constexpr int NST = PAIR ? 2 : 4;  // store instructions a lane issues per slice
-    // plain waves and the masks of the border forms: as in staged_apply2
-    bool plainWave = true;
-#pragma unroll
-    for (int q = 0; q < PER; ++q)
-        plainWave = plainWave && !undef[q] && (STENCIL != 2 || !(is_nn(xf[q]) || is_nn(yf[q])));
-    plainWave = __all(plainWave) != 0;
-    uint32_t mNnx[PER], mNny[PER], mUndef[PER];
-    uint32_t rowA[PER][STENCIL], rowS[PER][STENCIL];  // bilinear: aligned byte offset of a stencil row's pair, and its shift operand
-#pragma unroll
-    for (int q = 0; q < PER; ++q) {
-        mNnx[q] = nn_mask(xf[q]);
-        mNny[q] = nn_mask(yf[q]);
-        mUndef[q] = undef[q] ? 0xFFFFFFFFu : 0u;
-#pragma unroll
-        for (int i = 0; i < STENCIL; ++i) { rowA[q][i] = row[q][i] & ~3u; rowS[q][i] = row[q][i] << 3; }
-    }
-    // no fill value: comparisons with NaN never hold, the loops need no separate test
-    const float badCmp = hasBad ? te.bad : undefined_f();
-    dispatch_un<KMAX>(ring.un, plainWave, [&](auto unTag, auto plainTag) __attribute__((always_inline)) {
-        constexpr bool PLAIN = decltype(plainTag)::value;
-        ring.template run<decltype(unTag)::value, NST>([&](uint32_t z, const char* curb) __attribute__((always_inline)) {
-            const rsrc_t ro = ring.out(z);
-            float r[PER];
-            if constexpr (STENCIL == 1) {
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    const float v = lds_one<T>(curb, row[q][0], te.bad, hasBad);
-                    r[q] = PLAIN ? v : pick(mUndef[q], undefined_f(), v);
-                }
-            } else {
-                float s00[PER], s01[PER], s10[PER], s11[PER];
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    if constexpr (PLAIN) {
-                        lds_pair2_raw<T>(curb, rowA[q][0], rowS[q][0], s00[q], s01[q]);
-                        lds_pair2_raw<T>(curb, rowA[q][STENCIL - 1], rowS[q][STENCIL - 1], s10[q], s11[q]);
-                    } else {
-                        lds_pair2<T>(curb, rowA[q][0], rowS[q][0], te.bad, hasBad, s00[q], s01[q]);
-                        lds_pair2<T>(curb, rowA[q][STENCIL - 1], rowS[q][STENCIL - 1], te.bad, hasBad, s10[q], s11[q]);
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < PER; ++q) {
-                    const BilinearForms b = bilinear_forms(s00[q], s01[q], s10[q], s11[q], xf[q], yf[q]);
-                    r[q] = b.inter;
-                    if constexpr (PLAIN) {  // interior cell: undefined iff one of the four is the fill value (mifi_bad2nanf, then NaN spreads)
-                        // (the stored elements are integers, exact in float, and so is a fill value that can occur among them: the
-                        // product of the four differences is zero iff one element is the fill value -- one comparison and one
-                        // selection per output instead of four of each; without a fill value the product is NaN and never zero)
-                        const float anyBad = ((s00[q] - badCmp) * (s01[q] - badCmp)) * ((s10[q] - badCmp) * (s11[q] - badCmp));
-                        r[q] = (anyBad == 0.f) ? undefined_f() : b.inter;
-                    }
-                    if constexpr (!PLAIN) {
-                        r[q] = pick(mNnx[q], pick(mNny[q], s00[q], b.liny), pick(mNny[q], b.top, b.inter));
-                        r[q] = pick(mUndef[q], undefined_f(), r[q]);
-                    }
-                }
-            }
-            store_pair<T, PAIR>(ro, cellOff[0], cellOff[1], r[0], r[1], fillT);
-            store_pair<T, PAIR>(ro, cellOff[2], cellOff[3], r[2], r[3], fillT);
-        });
-    });
-}
-
-}  // namespace
 
 // the plan's staged form for slices of elemBytes-byte elements (2 or 1), built on first use; nullptr: none (the caller takes
 // the first staged form or the gather kernels)

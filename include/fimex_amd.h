@@ -357,6 +357,31 @@ int fimex_amd_interpolation2data_device(const float* d_in, size_t n, int cdmType
  *  combinations run the three passes on temporaries. */
 int fimex_amd_regrid_apply_typed_device(const fimex_amd_regrid_plan* plan, const void* d_in, int cdmType, size_t nz,
                                         double badValue, void* d_out, void* stream);
+/**
+ * A LIST of variables on one plan in one call: what nvar calls of fimex_amd_regrid_apply_device (of
+ * fimex_amd_regrid_apply_typed_device with badValue[i]) compute, byte for byte, for every plan kind and every numeric type those
+ * entries accept.  The reference calls CDMInterpolator::getDataSlice once per variable and time step
+ * (src/CDMInterpolator.cc:251-259); a writer hands one time step's variables of a grid over at once instead, each still an
+ * allocation of its own -- mostly surface fields of one slice, which alone are too short for the LDS-staged kernels.
+ *
+ * d_in, nz, badValue and d_out are HOST arrays of nvar entries, d_in[i] a device array [nz[i]][inY][inX] and d_out[i]
+ * [nz[i]][outY][outX]; the call only enqueues on `stream` and has read the four arrays when it returns.  nvar == 0 and
+ * nz[i] == 0 are successful no-ops that need no device (d_in[i], d_out[i] may then be NULL).  An input may appear more than once;
+ * outputs must not overlap each other or any input: such a call is refused and nothing is launched.  Pointers are aligned to the
+ * element size and nothing more.
+ *
+ * *path (NULL allowed): 1 = the slices ran through the list kernels of the second LDS-staged form, in launches of at most
+ * FIMEX_AMD_REGRID_MULTI_MAX_VARS variables; 0 = the per-variable calls ran inside the entry.  The list kernels run when the
+ * SUM of nz[] is a batch of that form -- nearest, bilinear and FIMEX_AMD_BICUBIC_FAST plans that hold it, at least 4 slices in
+ * all -- and, typed entry, the type has 1 or 2 bytes and every d_in[i] is 4-byte aligned.  Bicubic plans in the reference's
+ * arithmetic, forward plans, plans without a staged form, 4- and 8-byte types and shorter lists take path 0.
+ */
+#define FIMEX_AMD_REGRID_MULTI_MAX_VARS 64   /* variables one list launch takes; more run in several launches */
+int fimex_amd_regrid_apply_multi_device(const fimex_amd_regrid_plan* plan, size_t nvar, const float* const* d_in, const size_t* nz,
+                                        float* const* d_out, void* stream, int* path);
+int fimex_amd_regrid_apply_multi_typed_device(const fimex_amd_regrid_plan* plan, size_t nvar, const void* const* d_in, int cdmType,
+                                              const size_t* nz, const double* badValue, void* const* d_out, void* stream, int* path);
+/* The *_host forms are declared in fimex_amd_regrid_multi_host.h. */
 /** The same two conversions on host buffers (copied to the GPU and back), for callers that run their own 2-D processes
  *  on the float array in between. */
 int fimex_amd_data2interpolation_host(const void* in, int cdmType, size_t n, double badValue, float* out);
