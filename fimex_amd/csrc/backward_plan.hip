@@ -187,38 +187,6 @@ bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int
     return launch_typed_gather(plan, d_in, cdmType, nz, badValue, d_out, stream);
 }
 
-namespace {
-
-// the slices of a list, 0 where there are more than a launch counts
-size_t list_slices(const size_t* nz, size_t nvar)
-{
-    size_t total = 0;
-    for (size_t i = 0; i < nvar; ++i) {
-        if (nz[i] > 0xFFFFFFFFu - total) return 0;
-        total += nz[i];
-    }
-    return total;
-}
-
-// launch(first, count) on runs of the list that hold at most kSliceListMaxVars variables with slices
-template <class Launch>
-void for_list_launches(const size_t* nz, size_t nvar, Launch&& launch)
-{
-    size_t first = 0, held = 0;
-    for (size_t i = 0; i < nvar; ++i) {
-        if (nz[i] == 0) continue;
-        if (held == kSliceListMaxVars) {
-            launch(first, i - first);
-            first = i;
-            held = 0;
-        }
-        ++held;
-    }
-    if (held) launch(first, nvar - first);
-}
-
-}  // namespace
-
 bool launch_backward_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
                                 hipStream_t stream)
 {

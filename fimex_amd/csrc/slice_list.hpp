@@ -2,9 +2,10 @@
 // several variables, each an array of its own, and its kernels count LOGICAL slices 0 .. total - 1 -- the variables' levels one
 // variable after the other.  The z chunks cut the logical slices as they cut one array, so a chunk may begin and end inside a
 // variable.  Here: which variable and level a logical slice is, as a cursor that is seeded once per workgroup and then moved one
-// slice at a time.  Plain arithmetic without a HIP include, as staged_layout.hpp: the launchers build the table on the host, the
-// kernels move cursors on the device, and tests/test_slice_list.py compiles it with g++ and checks it on the CPU -- a cursor that
-// is wrong by one makes a base pointer of a foreign allocation.
+// slice at a time; and how a list of more variables than a launch takes is cut into launches.  Plain arithmetic without a HIP
+// include, as staged_layout.hpp: the launchers build the table on the host, the kernels move cursors on the device, and
+// tests/test_slice_list.py compiles it with g++ and checks it on the CPU -- a cursor that is wrong by one makes a base pointer
+// of a foreign allocation.
 #pragma once
 
 #include <cstddef>
@@ -50,6 +51,35 @@ inline bool build_slice_ends(const size_t* nz, size_t nvar, SliceEnds& e, uint32
         e.ends[e.nvar++] = (uint32_t)total;
     }
     return true;
+}
+
+// Host: the slices of a list, 0 where there are more than a launch counts
+inline size_t list_slices(const size_t* nz, size_t nvar)
+{
+    size_t total = 0;
+    for (size_t i = 0; i < nvar; ++i) {
+        if (nz[i] > 0xFFFFFFFFu - total) return 0;
+        total += nz[i];
+    }
+    return total;
+}
+
+// Host: a list of more variables than a launch takes is cut -- launch(first, count) on runs of the list that hold at most
+// kSliceListMaxVars variables with slices, so that build_slice_ends takes each of them
+template <class Launch>
+inline void for_list_launches(const size_t* nz, size_t nvar, Launch&& launch)
+{
+    size_t first = 0, held = 0;
+    for (size_t i = 0; i < nvar; ++i) {
+        if (nz[i] == 0) continue;
+        if (held == kSliceListMaxVars) {
+            launch(first, i - first);
+            first = i;
+            held = 0;
+        }
+        ++held;
+    }
+    if (held) launch(first, nvar - first);
 }
 
 // the cursor at logical slice l < ends[nvar - 1]: a scan over at most kSliceListMaxVars prefix sums

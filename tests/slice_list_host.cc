@@ -1,5 +1,6 @@
 // fimex_amd/csrc/slice_list.hpp for the CPU tests (tests/test_slice_list.py, through tests/slice_list_host.py): the table of a list
-// launch, and the two cursors of a workgroup walked over a z chunk the way SliceRing (staged2_ring.hpp) walks them.
+// launch, the cutting of a list into launches, and the two cursors of a workgroup walked over a z chunk the way SliceRing
+// (staged2_ring.hpp) walks them.
 #include "slice_list.hpp"
 
 using namespace fimex_amd;
@@ -22,6 +23,39 @@ int sl_build(const uint64_t* nz, uint64_t nvar, uint32_t* ends, uint32_t* index,
     *held = e.nvar;
     *total = t;
     return ok ? 1 : 0;
+}
+
+// list_slices of nz[nvar]
+uint64_t sl_list_slices(const uint64_t* nz, uint64_t nvar)
+{
+    size_t n[4096];
+    if (nvar > 4096) return 0;
+    for (uint64_t i = 0; i < nvar; ++i) n[i] = (size_t)nz[i];
+    return list_slices(n, (size_t)nvar);
+}
+
+// The launches for_list_launches cuts nz[nvar] into: first[k], count[k] of launch k (room for `room` of them), accepted[k] whether
+// build_slice_ends takes nz[first[k] .. first[k] + count[k]).  Returns the number of launches, -1 where there is no room.
+int sl_launches(const uint64_t* nz, uint64_t nvar, uint64_t* first, uint64_t* count, int32_t* accepted, int room)
+{
+    size_t n[4096];
+    if (nvar > 4096) return -1;
+    for (uint64_t i = 0; i < nvar; ++i) n[i] = (size_t)nz[i];
+    int made = 0;
+    bool full = false;
+    for_list_launches(n, (size_t)nvar, [&](size_t f, size_t c) {
+        if (made == room) {
+            full = true;
+            return;
+        }
+        SliceEnds e;
+        uint32_t index[kSliceListMaxVars];
+        size_t total = 0;
+        first[made] = f;
+        count[made] = c;
+        accepted[made++] = build_slice_ends(n + f, c, e, index, total) ? 1 : 0;
+    });
+    return full ? -1 : made;
 }
 
 // One workgroup's walk over the logical slices [z0, z1) of the list with a ring of `depth` slots: both cursors seeded at z0, the

@@ -27,6 +27,10 @@ def load():
     lib.sl_build.restype = ctypes.c_int
     lib.sl_walk.argtypes = [ptr, u64, u32, u32, u32, ptr, ptr, ptr, ptr, ptr]
     lib.sl_walk.restype = ctypes.c_int
+    lib.sl_list_slices.argtypes = [ptr, u64]
+    lib.sl_list_slices.restype = u64
+    lib.sl_launches.argtypes = [ptr, u64, ptr, ptr, ptr, ctypes.c_int]
+    lib.sl_launches.restype = ctypes.c_int
     _lib = lib
     return lib
 
@@ -39,6 +43,21 @@ def build(lib, nz):
     held, total = ctypes.c_uint32(0), ctypes.c_uint64(0)
     ok = lib.sl_build(nz.ctypes.data, len(nz), ends.ctypes.data, index.ctypes.data, ctypes.byref(held), ctypes.byref(total))
     return bool(ok), ends[:held.value].copy(), index[:held.value].copy(), int(total.value)
+
+
+def list_slices(lib, nz):
+    nz = np.ascontiguousarray(nz, dtype=np.uint64)
+    return int(lib.sl_list_slices(nz.ctypes.data, len(nz)))
+
+
+def launches(lib, nz):
+    """The launches for_list_launches cuts nz into, as rows of (first, count, whether build_slice_ends takes that run)."""
+    nz = np.ascontiguousarray(nz, dtype=np.uint64)
+    room = len(nz) + 1
+    first, count, ok = np.zeros(room, np.uint64), np.zeros(room, np.uint64), np.zeros(room, np.int32)
+    made = lib.sl_launches(nz.ctypes.data, len(nz), first.ctypes.data, count.ctypes.data, ok.ctypes.data, room)
+    assert made >= 0
+    return [(int(f), int(c), bool(a)) for f, c, a in zip(first[:made], count[:made], ok[:made])]
 
 
 def walk(lib, nz, z0, z1, depth):

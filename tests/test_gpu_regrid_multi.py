@@ -40,15 +40,17 @@ def _stream():
 class DeviceList:
     """Device copies of the variables `fields` ([nz_i][inY][inX] arrays of one dtype, nz_i may be 0) and their outputs of
     outLayer elements per slice.  pooled: two variables that share one allocation.  in_shift: variable -> bytes its source is
-    moved behind a 4-byte boundary."""
+    moved behind a 4-byte boundary; out_shift: the same for its output (a variable with an allocation of its own), with whole
+    guards on both sides still."""
 
-    def __init__(self, fields, outLayer, seed, pooled=(1, 2), in_shift=None):
+    def __init__(self, fields, outLayer, seed, pooled=(1, 2), in_shift=None, out_shift=None):
         import torch
         self.dtype = fields[0].dtype
         es = self.dtype.itemsize
         self.nz = [int(f.shape[0]) for f in fields]
         n = len(fields)
         in_shift = in_shift or {}
+        out_shift = out_shift or {}
         live = [i for i in range(n) if self.nz[i]]
         pooled = tuple(i for i in pooled if i in live) if len([i for i in pooled if i in live]) == 2 else ()
         inBytes = [f.nbytes for f in fields]
@@ -65,7 +67,7 @@ class DeviceList:
         single = [i for i in live if i not in pooled]
         if single:
             sizeIn = max(inBytes[i] for i in single) + 16
-            sizeOut = max(self.outBytes[i] for i in single) + 2 * guard
+            sizeOut = max(self.outBytes[i] for i in single) + 2 * guard + max(out_shift.values(), default=0)
             rng = np.random.default_rng(seed)
             for size, isOut in ((sizeIn, False), (sizeOut, True)):
                 blocks = sorted((torch.full((size,), SENTINEL, dtype=torch.uint8, device="cuda") for _ in single), key=lambda t: t.data_ptr())
@@ -75,9 +77,11 @@ class DeviceList:
                 for i, k in zip(single, perm):
                     t = blocks[k]
                     if isOut:
+                        s = out_shift.get(i, 0)
+                        assert t.data_ptr() % 4 == 0 and guard % 4 == 0
                         self.out_tensors.append(t)
-                        self.regions.append((len(self.out_tensors) - 1, guard, i))
-                        self.outs[i] = t.data_ptr() + guard
+                        self.regions.append((len(self.out_tensors) - 1, guard + s, i))
+                        self.outs[i] = t.data_ptr() + guard + s
                     else:
                         s = in_shift.get(i, 0)
                         t[s:s + inBytes[i]] = torch.from_numpy(np.ascontiguousarray(fields[i]).view(np.uint8).ravel()).cuda()
@@ -86,6 +90,7 @@ class DeviceList:
             if len(single) > 1:
                 for ptrs in ([self.ins[i] for i in single], [self.outs[i] for i in single]):
                     assert ptrs != sorted(ptrs)
+        assert all(i in single for i in out_shift), "out_shift: variables with an allocation of their own"
         if pooled:
             a, b = pooled
             oa = off16(0)

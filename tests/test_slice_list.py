@@ -82,6 +82,58 @@ def test_single_slice_variables_put_the_source_cursor_two_variables_ahead(lib):
     assert [tuple(r) for r in worked[7:]] == [(7, 0), (7, 1), (7, 2)]
 
 
+def _random_lists():
+    """lists of up to 300 entries of which a tenth to nine tenths are without slices, and the edges: zeros at either end, exactly
+    one, two and three launches of live variables, nothing but zeros"""
+    rng = np.random.default_rng(64)
+    for _ in range(400):
+        n = int(rng.integers(1, 301))
+        nz = rng.integers(1, 6, n)
+        nz[rng.random(n) < rng.uniform(0.1, 0.9)] = 0
+        yield nz
+    k = 64
+    for live in (1, k - 1, k, k + 1, 2 * k, 2 * k + 1, 3 * k, 3 * k + 2):
+        yield np.ones(live, np.int64)
+        yield np.concatenate([[0, 0], np.ones(live, np.int64), [0]])
+        yield np.stack([np.ones(live, np.int64), np.zeros(live, np.int64)], axis=1).ravel()  # a zero after every live variable
+    yield np.zeros(7, np.int64)
+
+
+def test_a_list_is_cut_into_launches_of_at_most_64_live_variables(lib):
+    """for_list_launches: every live variable lies in exactly one launch, the launches are in order and leave no gap between
+    them, none holds more than 64 live variables or none at all, every launch but the last is full, and build_slice_ends takes
+    each (first, count) as it stands."""
+    k = lib.sl_max_vars()
+    cut = 0
+    for nz in _random_lists():
+        got = host.launches(lib, nz)
+        live = np.flatnonzero(nz)
+        assert host.list_slices(lib, nz) == int(nz.sum())
+        assert len(got) == -(-len(live) // k), (list(nz), got)
+        owner = np.full(len(nz), -1)
+        end = None
+        for j, (first, count, accepted) in enumerate(got):
+            assert accepted and count > 0 and first + count <= len(nz), (list(nz), got)
+            assert end is None or first == end, "launches out of order or with a gap"
+            end = first + count
+            assert (owner[first:end] == -1).all()
+            owner[first:end] = j
+            held = int(np.count_nonzero(nz[first:end]))
+            assert 0 < held <= k and (held == k or j == len(got) - 1), (list(nz), got)
+            assert j == 0 or nz[first] != 0  # a launch after a cut begins with the variable that did not fit
+        if len(live):
+            assert (owner[live] >= 0).all() and (np.diff(owner[live]) >= 0).all() and end == len(nz)
+            assert got[0][0] == 0
+        cut += len(got) > 1
+    assert cut > 100
+
+
+def test_a_list_of_too_many_slices_counts_as_none(lib):
+    assert host.list_slices(lib, [2 ** 31, 0, 2 ** 31 - 1]) == 2 ** 32 - 1
+    assert host.list_slices(lib, [2 ** 31, 0, 2 ** 31]) == 0
+    assert host.list_slices(lib, []) == 0
+
+
 def test_chunks_outside_the_list_are_refused_by_the_walker(lib):
     assert host.walk(lib, [2, 3], 0, 6, 2) is None
     assert host.walk(lib, [0, 0], 0, 1, 2) is None
