@@ -1,5 +1,5 @@
-// Backward-mapping regrid for gfx950: plan classification, and the choice between the forms of the apply -- the two LDS-staged
-// ones (staged.hip, staged2.hip) and the per-lane gather (gather.hip).
+// Backward-mapping regrid for gfx950: plan classification, and the launch of the form of the apply that the rule names for a
+// call -- the two LDS-staged ones (staged.hip, staged2.hip) or the per-lane gather (gather.hip).  The rule: backward_dispatch.hpp.
 //
 // The reference keeps two doubles per output cell and re-derives floor / fraction / border class for every cell of every call
 // (src/interpolation.c:862-1028); here that runs once per plan (plan.hpp).
@@ -106,9 +106,9 @@ void build_backward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const 
     FA_HIP(hipStreamSynchronize(stream));
     plan.info.undefinedCells = (size_t)h.undefined;
     plan.info.borderCells = (size_t)h.border;
-    // bilinear: also the LDS-staged form (staged.hip); plans whose tiles do not fit keep the gather kernel only
-    if (tuning("STAGED", 1) != 0 && (plan.kind != PlanKind::Nearest || tuning("STAGED_NEAREST", 1) != 0) &&
-        build_staged_plan(plan, d_px, d_py, stream)) {
+    // also the LDS-staged form (staged.hip); plans whose tiles do not fit keep the gather kernel only
+    const dispatch::Switches sw = dispatch_switches();
+    if (dispatch::builds_first(sw, plan_facts(plan)) && build_staged_plan(plan, d_px, d_py, stream)) {
         const auto& s = plan.staged;  // the staged kernel reads LDS offsets instead of pos, plus the tile tables
         plan.info.planBytes = plan.info.planBytes - plan.pos.bytes() + s.ldsA.bytes() + s.ldsB.bytes() + s.tileHdr.bytes() +
                               (size_t)s.nTiles * 2 * 4 * 48;
@@ -116,12 +116,8 @@ void build_backward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const 
         plan.info.tileW = s.tileW;
         plan.info.tileH = s.tileH;
     }
-    // the second staged form (staged2.hip) serves float slices; the first one stays for 1- and 2-byte stored types
-    // (bicubic keeps the first form where it exists -- 32 x 16 tiles at four workgroups per CU suit its arithmetic -- and takes
-    // the second one for the source widths the first cannot stage, inX % 4 != 0)
-    const int second = tuning("STAGED2", 1);
-    const bool wantSecond = second >= 2 || (second == 1 && (plan.kind != PlanKind::Bicubic || !plan.staged.valid || plan.bicubicFast));
-    if (tuning("STAGED", 1) != 0 && wantSecond && build_staged2_plan(plan, d_px, d_py, stream)) {
+    // the second staged form (staged2.hip), where the plan will prefer it for float slices
+    if (dispatch::builds_second(sw, plan_facts(plan)) && build_staged2_plan(plan, d_px, d_py, stream)) {
         const auto& s = plan.staged2;
         const size_t perCell = plan.kind == PlanKind::Nearest ? 0 : (plan.kind == PlanKind::Bilinear ? plan.xf.bytes() + plan.yf.bytes()
                                                                                                        : plan.xfd.bytes() + plan.yfd.bytes());
@@ -137,79 +133,77 @@ void build_backward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const 
     }
 }
 
-// whether a float batch of nz slices takes the second staged form:
-// the staged kernel pays a per-tile set-up (row table, chunk list) that only amortises over a few slices
-// (a bicubic plan in the reference's arithmetic that holds both forms runs the first one)
-static bool takes_second_form(const fimex_amd_regrid_plan& plan, size_t nz)
+// the one reader of the switches of backward_dispatch.hpp (tests/test_backward_dispatch.py holds every other file to that)
+dispatch::Switches dispatch_switches()
 {
-    const bool second = plan.staged2.valid && (plan.kind != PlanKind::Bicubic || plan.bicubicFast || !plan.staged.valid || tuning("STAGED2", 1) >= 2);
-    return second && tuning("STAGED", 1) != 0 && tuning("STAGED2", 1) != 0 && nz >= staged_min_nz();
+    dispatch::Switches sw{};
+    sw.staged = tuning("STAGED", 1);
+    sw.stagedNearest = tuning("STAGED_NEAREST", 1);
+    sw.staged2 = tuning("STAGED2", 1);
+    sw.typedFused = tuning("TYPED_FUSED", 1);
+    sw.typedStaged = tuning("TYPED_STAGED", 1);
+    sw.typedStaged2 = tuning("TYPED_STAGED2", 1);
+    sw.vectorFused = tuning("VECTOR_FUSED", 1);
+    sw.stagedMinNz = (uint64_t)tuning("STAGED_MIN_NZ", 4);
+    return sw;
 }
 
 int backward_launch_order(const fimex_amd_regrid_plan& plan, size_t nz)
 {
-    return takes_second_form(plan, nz) ? staged2_float_launch_order(plan, nz) : -1;
+    const bool second = dispatch::float_apply(dispatch_switches(), plan_facts(plan), nz) == dispatch::FloatApply::Second;
+    return second ? staged2_float_launch_order(plan, nz) : -1;
 }
 
 void launch_backward_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream)
 {
     if (nz == 0) return;
     FA_REQUIRE(nz <= 0xFFFFFFFFu, "too many slices");
-    if (takes_second_form(plan, nz)) {
-        launch_staged2_apply(plan, d_in, nz, d_out, stream);
-        return;
+    switch (dispatch::float_apply(dispatch_switches(), plan_facts(plan), nz)) {
+    case dispatch::FloatApply::Second: launch_staged2_apply(plan, d_in, nz, d_out, stream); break;
+    case dispatch::FloatApply::First: launch_staged_apply(plan, d_in, nz, d_out, stream); break;
+    case dispatch::FloatApply::Gather: launch_backward_gather(plan, d_in, nz, d_out, stream); break;
     }
-    if (plan.staged.valid && tuning("STAGED", 1) != 0 && nz >= staged_min_nz()) {
-        launch_staged_apply(plan, d_in, nz, d_out, stream);
-        return;
-    }
-    launch_backward_gather(plan, d_in, nz, d_out, stream);
 }
 
-// Fused stored-type apply (backward plans: 1- and 2-byte integer types and int32); returns false for everything else
-// (the caller then runs the three-pass sequence: to float, regrid, from float).
+// One kernel on the stored type where the rule has one; false: the caller runs the three passes (to float, regrid, from float)
 bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                         hipStream_t stream)
 {
     // forward plans with long buckets: the LDS-staged forward kernel on the stored type (forward_tiled.hip)
     if (plan.kind == PlanKind::Forward) return launch_forward_tiled_typed(plan, d_in, cdmType, nz, badValue, d_out, stream);
-    // 1- and 2-byte types through the LDS-staged kernels (the same dispatch rule as for floats): the second staged form
-    // (staged2.hip, nearest and bilinear), else the first one
-    if (plan.kind != PlanKind::Forward && tuning("TYPED_FUSED", 1) != 0 && tuning("STAGED", 1) != 0 && tuning("TYPED_STAGED", 1) != 0 &&
-        tuning("TYPED_STAGED2", 1) != 0 && nz >= staged_min_nz() && launch_staged2_apply_typed(plan, d_in, cdmType, nz, badValue, d_out, stream))
-        return true;
-    if (plan.kind != PlanKind::Forward && tuning("TYPED_FUSED", 1) != 0 && plan.staged.valid && tuning("STAGED", 1) != 0 && tuning("TYPED_STAGED", 1) != 0 &&
-        nz >= staged_min_nz() && (plan.kind != PlanKind::Nearest || tuning("STAGED_NEAREST", 1) != 0) &&
-        launch_staged_apply_typed(plan, d_in, cdmType, nz, badValue, d_out, stream))
-        return true;
-    // bicubic: the LDS-staged float kernel between two conversion passes beats a 16-load gather on the stored type
-    if (plan.kind == PlanKind::Forward || (plan.kind == PlanKind::Bicubic && tuning("TYPED_FUSED", 1) < 2) || tuning("TYPED_FUSED", 1) == 0) return false;
-    return launch_typed_gather(plan, d_in, cdmType, nz, badValue, d_out, stream);
+    const dispatch::TypedCandidates t = dispatch::typed_apply(dispatch_switches(), plan_facts(plan), {nz, cdmType, cdmType, aligned4(d_in)});
+    for (int i = 0; i < t.n; ++i) {
+        switch (t.c[i]) {
+        case dispatch::TypedApply::Second:  // (the plan may turn out to have no form for this element size)
+            if (launch_staged2_apply_typed(plan, d_in, cdmType, nz, badValue, d_out, stream)) return true;
+            break;
+        case dispatch::TypedApply::First: launch_staged_apply_typed(plan, d_in, cdmType, nz, badValue, d_out, stream); return true;
+        case dispatch::TypedApply::Gather: launch_typed_gather(plan, d_in, cdmType, nz, badValue, d_out, stream); return true;
+        case dispatch::TypedApply::ThreePasses: return false;
+        }
+    }
+    return false;
 }
 
 bool launch_backward_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
                                 hipStream_t stream)
 {
-    const size_t total = list_slices(nz, nvar);
-    if (plan.kind == PlanKind::Forward || !takes_second_form(plan, total) || !staged2_list_serves(plan)) return false;
+    const dispatch::Switches sw = dispatch_switches();
+    if (!dispatch::float_list(sw, plan_facts(plan), list_slices(nz, nvar)) || !staged2_list_serves(plan)) return false;
     for_list_launches(nz, nvar, [&](size_t first, size_t count) {
-        launch_staged2_apply_list(plan, count, d_in + first, nz + first, d_out + first, stream);
+        launch_staged2_apply_list(plan, sw, count, d_in + first, nz + first, d_out + first, stream);
     });
     return true;
 }
 
-// (the switches and the batch length of launch_typed_apply's second staged form; the types, the plans and the alignment of
-// launch_staged2_apply_typed)
 bool launch_typed_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const void* const* d_in, int cdmType, const size_t* nz,
                              const double* badValue, void* const* d_out, hipStream_t stream)
 {
-    const size_t total = list_slices(nz, nvar);
-    if (plan.kind == PlanKind::Forward || tuning("TYPED_FUSED", 1) == 0 || tuning("STAGED", 1) == 0 || tuning("TYPED_STAGED", 1) == 0 ||
-        tuning("TYPED_STAGED2", 1) == 0 || total < staged_min_nz())
+    bool aligned = true;
+    for (size_t i = 0; i < nvar; ++i) aligned = aligned && (nz[i] == 0 || aligned4(d_in[i]));
+    if (!dispatch::typed_list(dispatch_switches(), plan_facts(plan), {list_slices(nz, nvar), cdmType, cdmType, aligned}) ||
+        !staged2_list_typed_serves(plan, cdmType, stream))
         return false;
-    for (size_t i = 0; i < nvar; ++i)
-        if (nz[i] != 0 && reinterpret_cast<uintptr_t>(d_in[i]) % 4 != 0) return false;
-    if (!staged2_list_typed_serves(plan, cdmType, stream)) return false;
     for_list_launches(nz, nvar, [&](size_t first, size_t count) {
         launch_staged2_apply_list_typed(plan, count, d_in + first, cdmType, nz + first, badValue + first, d_out + first, stream);
     });

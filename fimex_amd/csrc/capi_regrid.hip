@@ -223,8 +223,10 @@ int fimex_amd_regrid_plan_tune_device(fimex_amd_regrid_plan* plan, const float* 
         // for the second launch order (the choices made on a longer batch stay as they are).  A batch that has two shapes but is too
         // short for the second order chooses the shape again and leaves the order alone: its own launches do not read it.
         const bool shapes = plan->staged2Alt.valid;
-        const bool orders = backward_launch_order(*plan, nz) >= 0 && chunk_xcd_chunk_count(nz, staged2_zpb()) != 0;
-        if (nz < staged_min_nz() || !plan->staged2.valid || !(shapes || orders)) return;
+        const dispatch::Switches sw = dispatch_switches();
+        const bool orders = dispatch::float_apply(sw, plan_facts(*plan), nz) == dispatch::FloatApply::Second &&
+                            chunk_xcd_chunk_count(nz, staged2_zpb()) != 0;
+        if (!dispatch::tune_has_choice(sw, plan_facts(*plan), nz, shapes, orders)) return;
         FA_REQUIRE(d_in != nullptr && d_out != nullptr, "NULL device buffer");
         require_current_device(plan->device);
         hipStream_t st = as_stream(stream);

@@ -20,7 +20,7 @@ namespace fimex_amd {
 int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
                       float* d_uOut, float* d_vOut, hipStream_t stream)
 {
-    if (staged2_vector_serves(plan, nz)) {
+    if (dispatch::vector_fused(dispatch_switches(), plan_facts(plan), nz)) {
         launch_staged2_apply_vector(plan, vec, d_u, d_v, nz, d_uOut, d_vOut, stream);
         return 1;
     }
@@ -37,7 +37,9 @@ int apply_vector_pair(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_
 int apply_vector_pair_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, int uType, double uBad,
                             const void* d_v, int vType, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream)
 {
-    if (uType == vType && launch_staged2_apply_vector_typed(plan, vec, d_u, d_v, uType, uBad, vBad, nz, d_uOut, d_vOut, stream)) return 2;
+    if (dispatch::vector_typed_fused(dispatch_switches(), plan_facts(plan), {nz, uType, vType, aligned4(d_u) && aligned4(d_v)}) &&
+        launch_staged2_apply_vector_typed(plan, vec, d_u, d_v, uType, uBad, vBad, nz, d_uOut, d_vOut, stream))
+        return 2;
     const size_t nIn = nz * plan.inX * plan.inY, nOut = nz * plan.outX * plan.outY;
     DeviceArray<float> fu(nIn), fv(nIn), fuOut(nOut), fvOut(nOut);
     launch_data2interpolation(d_u, uType, nIn, uBad, fu.get(), stream);

@@ -266,17 +266,16 @@ void launch_backward_gather(const fimex_amd_regrid_plan& plan, const float* d_in
     FA_HIP(hipGetLastError());
 }
 
-// The same kernel on a variable's stored type, for 1- and 2-byte integer types and int32; returns false for everything else (the
-// caller then runs the three-pass sequence: to float, regrid, from float).
-bool launch_typed_gather(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+// The same kernel on a variable's stored type, for 1- and 2-byte integer types and int32 (everything else runs the three-pass
+// sequence: to float, regrid, from float).
+void launch_typed_gather(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                          hipStream_t stream)
 {
-    if (!(cdmType == FIMEX_AMD_CDM_CHAR || cdmType == FIMEX_AMD_CDM_UCHAR || cdmType == FIMEX_AMD_CDM_SHORT ||
-          cdmType == FIMEX_AMD_CDM_USHORT || cdmType == FIMEX_AMD_CDM_INT))
-        return false;
-    if (nz == 0) return true;
+    if (nz == 0) return;
     FA_REQUIRE(nz <= 0xFFFFFFFFu, "too many slices");
-    if (8 * 4 * std::max(plan.inX * plan.inY, plan.outX * plan.outY) > 0xFFFFFFFFull) return false;  // 8 slices behind one descriptor
+    FA_REQUIRE((dispatch::staged_elem_bytes(cdmType) != 0 || cdmType == FIMEX_AMD_CDM_INT) &&
+                   8 * 4 * std::max(plan.inX * plan.inY, plan.outX * plan.outY) <= 0xFFFFFFFFull,  // 8 slices behind one descriptor
+               "typed gather: not a call of this kernel (typed_gather, backward_dispatch.hpp)");
     dim3 grid;
     const ApplyArgs a = make_args(plan, d_in, nz, d_out, grid);
     const float bad = (float)badValue;
@@ -291,7 +290,6 @@ bool launch_typed_gather(const fimex_amd_regrid_plan& plan, const void* d_in, in
     case FIMEX_AMD_CDM_USHORT: go((unsigned short)0); break;
     default: go((int)0); break;
     }
-    return true;
 }
 
 }  // namespace fimex_amd

@@ -18,6 +18,7 @@
 //             order so that sums add in the reference's push_back order.
 #pragma once
 
+#include "backward_dispatch.hpp"
 #include "common.hpp"
 #include "staged_layout.hpp"
 
@@ -30,8 +31,7 @@ constexpr uint32_t kInvalidPos = 0xFFFFFFFFu;
 // source slices are addressed with 32-bit cell offsets (and 32-bit byte offsets in the kernels)
 constexpr size_t kMaxSliceCells = (size_t(1) << 30) - 1;
 
-enum class PlanKind { Nearest, Bilinear, Bicubic, Forward };
-
+// (PlanKind: backward_dispatch.hpp)
 enum class Aggregate : int { Sum = 0, Mean = 1, Median = 2, Max = 3, Min = 4 };
 
 }  // namespace fimex_amd
@@ -150,7 +150,14 @@ struct fimex_amd_merge_plan {
 
 namespace fimex_amd {
 
-// backward_plan.hip: classification, and the choice between the staged forms and the gather
+// backward_plan.hip: classification, and the launches of the kernel that backward_dispatch.hpp names for a call.
+// dispatch_switches is the only reader of the eight experiment switches of that rule; a caller fills them once and asks the rule.
+dispatch::Switches dispatch_switches();
+inline dispatch::PlanFacts plan_facts(const fimex_amd_regrid_plan& plan)
+{
+    return {plan.kind, plan.funcType, plan.bicubicFast, plan.staged.valid, plan.staged2.valid, plan.inX, plan.inY, plan.outX, plan.outY};
+}
+inline bool aligned4(const void* p) { return reinterpret_cast<uintptr_t>(p) % 4 == 0; }
 void build_backward_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
 void launch_backward_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
 // the LaunchOrder (staged_layout.hpp) of launch_backward_apply's launch of nz slices; -1: not a float launch of the second staged form
@@ -159,21 +166,20 @@ bool launch_typed_apply(const fimex_amd_regrid_plan& plan, const void* d_in, int
                         hipStream_t stream);
 // A list of variables, variable i an array of nz[i] slices of its own, through the second staged form's list kernels
 // (staged2_list.hip, staged2_list_typed.hip) in launches of at most kSliceListMaxVars variables.  false, and nothing launched: the
-// slices together are no batch of the second staged form (the rule of launch_backward_apply / launch_typed_apply on the SUM of
-// nz[]), or a source of a stored type is not 4-byte aligned; the caller runs the variables one by one.
+// rule (float_list / typed_list, on the SUM of nz[]) or the list kernels' shapes say no; the caller runs the variables one by one.
 bool launch_backward_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
                                 hipStream_t stream);
 bool launch_typed_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const void* const* d_in, int cdmType, const size_t* nz,
                              const double* badValue, void* const* d_out, hipStream_t stream);
 // gather.hip: the per-lane gather kernel on float slices and on stored types
 void launch_backward_gather(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
-bool launch_typed_gather(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+void launch_typed_gather(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                          hipStream_t stream);
 
 // staged.hip
 bool build_staged_plan(fimex_amd_regrid_plan& plan, const double* d_px, const double* d_py, hipStream_t stream);
 void launch_staged_apply(const fimex_amd_regrid_plan& plan, const float* d_in, size_t nz, float* d_out, hipStream_t stream);
-bool launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+void launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                hipStream_t stream);
 
 // staged2_plan.hip
@@ -184,23 +190,20 @@ int staged2_float_launch_order(const fimex_amd_regrid_plan& plan, size_t nz);  /
 // staged2_list.hip, staged2_list_typed.hip: one launch on the slices of nvar <= kSliceListMaxVars variables; `serves`: the list
 // kernels exist for the workgroup shape the plan's launches run (and, stored types, the plan has a form for the type)
 bool staged2_list_serves(const fimex_amd_regrid_plan& plan);
-void launch_staged2_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
-                               hipStream_t stream);
+void launch_staged2_apply_list(const fimex_amd_regrid_plan& plan, const dispatch::Switches& sw, size_t nvar, const float* const* d_in,
+                               const size_t* nz, float* const* d_out, hipStream_t stream);
 bool staged2_list_typed_serves(const fimex_amd_regrid_plan& plan, int cdmType, hipStream_t stream);
 void launch_staged2_apply_list_typed(const fimex_amd_regrid_plan& plan, size_t nvar, const void* const* d_in, int cdmType, const size_t* nz,
                                      const double* badValue, void* const* d_out, hipStream_t stream);
-// staged2_vector.hip: both components of a vector pair regridded and rotated in one launch; `serves` is the dispatch rule
-// (nearest / bilinear plans with the second staged form, batches of staged_min_nz() pairs and more, VECTOR_FUSED not 0)
-bool staged2_vector_serves(const fimex_amd_regrid_plan& plan, size_t nz);
+// staged2_vector.hip: both components of a vector pair regridded and rotated in one launch (the rule: vector_fused)
 void launch_staged2_apply_vector(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
                                  float* d_uOut, float* d_vOut, hipStream_t stream);
-// staged2_typed.hip
+// staged2_typed.hip; false, nothing launched: the plan has no form for slices of this element size (staged2_typed_form)
 bool launch_staged2_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                 hipStream_t stream);
 
 // staged2_vector_typed.hip: a vector pair on its stored type (short / unsigned short, both components in one type) regridded and
-// rotated in one launch; false: not served, nothing launched (other types, plans without the 2-byte form, unaligned sources,
-// batches below staged_min_nz(), switched off in the tuning build)
+// rotated in one launch (the rule: vector_typed_fused); false, nothing launched: the plan has no 2-byte form
 bool launch_staged2_apply_vector_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, const void* d_v,
                                        int cdmType, double uBad, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream);
 
@@ -409,10 +412,6 @@ void release_host_pipes();
 // experiment switches: the measured default in the product library; the tuning build (-DFIMEX_AMD_TUNING) reads FIMEX_AMD_<NAME>
 // from the environment at every call, so that one process can sweep settings (capi.hip)
 int tuning(const char* name, int fallback);
-
-// batches shorter than this take the gather kernels: the staged kernels pay a per-tile set-up (chunk list, per-output plan)
-// that only amortises over a few slices (launch_backward_apply and fimex_amd_regrid_plan_tune_device share the rule)
-inline size_t staged_min_nz() { return (size_t)tuning("STAGED_MIN_NZ", 4); }
 
 // slices per z chunk of the second form's float launches in tile-major and chunk-per-XCD order (staged2_z_chunks, staged2.hpp, and
 // fimex_amd_regrid_plan_tune_device share it)

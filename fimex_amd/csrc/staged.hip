@@ -601,15 +601,13 @@ void launch_staged_apply(const fimex_amd_regrid_plan& plan, const float* d_in, s
 }
 
 // The staged kernels on a variable's stored type (1- and 2-byte integers): what gather_apply on a stored type (gather.hip) does with
-// gathers, through the LDS image.  false: not applicable (type, alignment), the caller takes another path.
-bool launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
+// gathers, through the LDS image.
+void launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                hipStream_t stream)
 {
-    if (!plan.staged.valid) return false;
-    if (!(cdmType == FIMEX_AMD_CDM_CHAR || cdmType == FIMEX_AMD_CDM_UCHAR || cdmType == FIMEX_AMD_CDM_SHORT || cdmType == FIMEX_AMD_CDM_USHORT))
-        return false;
     // 4-byte DMA pieces: slices and row segments start on 4-byte boundaries (inX % 4 == 0 holds for every staged plan)
-    if (reinterpret_cast<uintptr_t>(d_in) % 4 != 0) return false;
+    FA_REQUIRE(plan.staged.valid && dispatch::staged_elem_bytes(cdmType) != 0 && aligned4(d_in),
+               "staged typed: not a call of this kernel (typed_first, backward_dispatch.hpp)");
     StagedArgs a{};
     a.in = d_in;
     a.out = d_out;
@@ -622,7 +620,6 @@ bool launch_staged_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_
     case FIMEX_AMD_CDM_SHORT: launch_staged_t<short>(plan, a, nz, stream); break;
     default: launch_staged_t<unsigned short>(plan, a, nz, stream); break;
     }
-    return true;
 }
 
 }  // namespace fimex_amd

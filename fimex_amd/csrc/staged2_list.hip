@@ -52,11 +52,11 @@ bool list_shape(const fimex_amd_regrid_plan& plan, const Staged2Plan& s)
 
 bool staged2_list_serves(const fimex_amd_regrid_plan& plan)
 {
-    return plan.staged2.valid && list_shape(plan, staged2_shape_of(plan));
+    return list_shape(plan, staged2_shape_of(plan));
 }
 
-void launch_staged2_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, const float* const* d_in, const size_t* nz, float* const* d_out,
-                               hipStream_t stream)
+void launch_staged2_apply_list(const fimex_amd_regrid_plan& plan, const dispatch::Switches& sw, size_t nvar, const float* const* d_in,
+                               const size_t* nz, float* const* d_out, hipStream_t stream)
 {
     SliceListArgs l{};
     uint32_t index[kSliceListMaxVars];
@@ -70,7 +70,7 @@ void launch_staged2_apply_list(const fimex_amd_regrid_plan& plan, size_t nvar, c
     // float arithmetic only for the variables whose own call would run this form (launch_backward_apply)
     if (plan.kind == PlanKind::Bicubic)
         for (uint32_t k = 0; k < l.e.nvar; ++k)
-            if (nz[index[k]] < staged_min_nz()) l.exactMask |= 1ull << k;
+            if (dispatch::float_apply(sw, plan_facts(plan), nz[index[k]]) != dispatch::FloatApply::Second) l.exactMask |= 1ull << k;
     const Staged2Plan& s = staged2_shape_of(plan);
     FA_REQUIRE(list_shape(plan, s), "staged2 list: no kernel for this workgroup shape");
     Staged2Args a = staged2_args(plan, s, nullptr, nullptr, 4, total);

@@ -43,27 +43,19 @@ void launch_list_shape(const Staged2Plan& s, const Staged2Args& a, const TypedEd
     pair ? go(&staged_apply2_list_typed<STENCIL, 512, 6, T, true, 2>) : go(&staged_apply2_list_typed<STENCIL, 512, 6, T, false, 2>);
 }
 
-uint32_t list_elem_bytes(int cdmType)
-{
-    if (cdmType == FIMEX_AMD_CDM_SHORT || cdmType == FIMEX_AMD_CDM_USHORT) return 2;
-    return (cdmType == FIMEX_AMD_CDM_CHAR || cdmType == FIMEX_AMD_CDM_UCHAR) ? 1u : 0u;
-}
-
 }  // namespace
 
-// whether the list kernel serves this plan and type: the types and plans launch_staged2_apply_typed serves, on the shapes above
+// the two facts the rule (typed_list) leaves to the launcher: the plan has a form for the type, of a shape above
 bool staged2_list_typed_serves(const fimex_amd_regrid_plan& plan, int cdmType, hipStream_t stream)
 {
-    const uint32_t eb = list_elem_bytes(cdmType);
-    if (eb == 0) return false;
-    const Staged2Plan* form = staged2_typed_form(plan, eb, stream);
+    const Staged2Plan* form = staged2_typed_form(plan, dispatch::staged_elem_bytes(cdmType), stream);
     return form && list_shape(*form);
 }
 
 void launch_staged2_apply_list_typed(const fimex_amd_regrid_plan& plan, size_t nvar, const void* const* d_in, int cdmType, const size_t* nz,
                                      const double* badValue, void* const* d_out, hipStream_t stream)
 {
-    const uint32_t eb = list_elem_bytes(cdmType);
+    const uint32_t eb = dispatch::staged_elem_bytes(cdmType);
     const Staged2Plan* form = eb ? staged2_typed_form(plan, eb, stream) : nullptr;
     FA_REQUIRE(form && list_shape(*form), "staged2 typed list: no kernel for this plan and type");
     SliceListArgs l{};

@@ -198,7 +198,7 @@ struct SliceRing : Slices {
         if constexpr (Slices::kList) Slices::step(this->list, this->cur);
     }
     // List form, FIMEX_AMD_BICUBIC_FAST plans: whether the slice in work is computed in the reference's arithmetic after all.  A
-    // variable of fewer than staged_min_nz() slices, called on its own, runs the gather kernel, which knows no other arithmetic;
+    // variable of fewer than STAGED_MIN_NZ slices, called on its own, runs the gather kernel, which knows no other arithmetic;
     // in a list it gets the same bytes.
     __device__ __forceinline__ bool exact_slice() const
     {

@@ -23,8 +23,9 @@ namespace fimex_amd {
 // the first staged form or the gather kernels)
 const Staged2Plan* staged2_typed_form(const fimex_amd_regrid_plan& plan, uint32_t elemBytes, hipStream_t stream)
 {
-    if (plan.kind != PlanKind::Nearest && plan.kind != PlanKind::Bilinear) return nullptr;
-    if ((plan.inX * plan.inY * elemBytes) % 4 != 0) return nullptr;  // slices start on 4-byte boundaries (LDS-DMA)
+    FA_REQUIRE((elemBytes == 1 || elemBytes == 2) && (plan.kind == PlanKind::Nearest || plan.kind == PlanKind::Bilinear) &&
+                   (plan.inX * plan.inY * elemBytes) % 4 == 0,
+               "staged2 typed: no form for this plan and element size (typed_second, backward_dispatch.hpp)");
     const int idx = elemBytes == 2 ? 0 : 1;
     std::lock_guard<std::mutex> lock(plan.typed2.mtx);
     Staged2Plan& form = plan.typed2.form[idx];
@@ -81,14 +82,12 @@ void launch_typed(bool nearest, const Staged2Plan& s, const Staged2Args& a, cons
 }  // namespace
 
 // data2InterpolationArray + interpolateValues + interpolationArray2Data (src/CDMInterpolator.cc:115-124, 251-285) on slices of
-// 1- and 2-byte integers, nearest and bilinear, through the second staged form.  false: not applicable, the caller goes on.
+// 1- and 2-byte integers, nearest and bilinear, through the second staged form.  false: the plan has no such form, the caller goes on.
 bool launch_staged2_apply_typed(const fimex_amd_regrid_plan& plan, const void* d_in, int cdmType, size_t nz, double badValue, void* d_out,
                                 hipStream_t stream)
 {
-    if (!(cdmType == FIMEX_AMD_CDM_CHAR || cdmType == FIMEX_AMD_CDM_UCHAR || cdmType == FIMEX_AMD_CDM_SHORT || cdmType == FIMEX_AMD_CDM_USHORT))
-        return false;
-    const uint32_t eb = (cdmType == FIMEX_AMD_CDM_SHORT || cdmType == FIMEX_AMD_CDM_USHORT) ? 2u : 1u;
-    if (reinterpret_cast<uintptr_t>(d_in) % 4 != 0) return false;
+    const uint32_t eb = dispatch::staged_elem_bytes(cdmType);
+    FA_REQUIRE(eb != 0 && aligned4(d_in), "staged2 typed: not a call of this kernel (typed_second, backward_dispatch.hpp)");
     if (nz == 0) return true;
     const Staged2Plan* form = staged2_typed_form(plan, eb, stream);
     if (!form) return false;

@@ -191,14 +191,6 @@ void launch_shape(const Staged2Plan& s, const Staged2VectorArgs& va, dim3 grid, 
 
 }  // namespace
 
-bool staged2_vector_serves(const fimex_amd_regrid_plan& plan, size_t nz)
-{
-    // (the plans of the coordinate searches are nearest plans too; they keep the three launches)
-    const bool method = plan.funcType == FIMEX_AMD_INTERPOL_NEAREST_NEIGHBOR || plan.funcType == FIMEX_AMD_INTERPOL_BILINEAR;
-    return plan.staged2.valid && method && nz >= staged_min_nz() &&
-           tuning("STAGED", 1) != 0 && tuning("STAGED2", 1) != 0 && tuning("VECTOR_FUSED", 1) != 0;
-}
-
 void launch_staged2_apply_vector(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const float* d_u, const float* d_v, size_t nz,
                                  float* d_uOut, float* d_vOut, hipStream_t stream)
 {

@@ -257,18 +257,12 @@ void launch_shape(const Staged2Plan& s, const Staged2VectorTypedArgs& va, bool p
 
 }  // namespace
 
-// false: not served (the caller takes the chain around the float pair entry), nothing launched
+// false: the plan has no 2-byte form (the caller takes the chain around the float pair entry), nothing launched
 bool launch_staged2_apply_vector_typed(const fimex_amd_regrid_plan& plan, const fimex_amd_vector_plan& vec, const void* d_u, const void* d_v,
                                        int cdmType, double uBad, double vBad, size_t nz, void* d_uOut, void* d_vOut, hipStream_t stream)
 {
-    if (!(cdmType == FIMEX_AMD_CDM_SHORT || cdmType == FIMEX_AMD_CDM_USHORT)) return false;
-    // (the plans of the coordinate searches are nearest plans too; they keep the chain)
-    if (!(plan.funcType == FIMEX_AMD_INTERPOL_NEAREST_NEIGHBOR || plan.funcType == FIMEX_AMD_INTERPOL_BILINEAR)) return false;
-    if (reinterpret_cast<uintptr_t>(d_u) % 4 != 0 || reinterpret_cast<uintptr_t>(d_v) % 4 != 0) return false;  // slices start on 4-byte boundaries (LDS-DMA)
-    if (nz < staged_min_nz() || nz > 0xFFFFFFFFu) return false;
-    if (tuning("STAGED", 1) == 0 || tuning("TYPED_FUSED", 1) == 0 || tuning("TYPED_STAGED", 1) == 0 || tuning("TYPED_STAGED2", 1) == 0 ||
-        tuning("VECTOR_FUSED", 1) == 0)
-        return false;
+    FA_REQUIRE(dispatch::staged_elem_bytes(cdmType) == 2 && aligned4(d_u) && aligned4(d_v) && nz <= 0xFFFFFFFFu,
+               "staged2 typed pairs: not a call of this kernel (vector_typed_fused, backward_dispatch.hpp)");
     const Staged2Plan* form = staged2_typed_form(plan, 2, stream);
     if (!form) return false;
     const Staged2Plan& s = *form;

@@ -25,7 +25,7 @@ GEOMETRY = {
     "border": ((400, 300, 200, 200), lambda: cases.backward_positions(400, 300, 200, 200, seed=600)),
     "coord": ((300, 200, 157, 211), lambda: cases.backward_positions(300, 200, 157, 211, seed=100 + oracle.COORD_NN)),
 }
-MIN_NZ = 4  # staged_min_nz()
+MIN_NZ = 4  # STAGED_MIN_NZ
 
 
 def _scattered():

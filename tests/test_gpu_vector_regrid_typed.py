@@ -22,7 +22,7 @@ import oracle
 
 pytestmark = pytest.mark.gpu
 
-MIN_NZ = 4  # staged_min_nz()
+MIN_NZ = 4  # STAGED_MIN_NZ
 METHODS = [oracle.NEAREST, oracle.BILINEAR]
 METHOD_IDS = ["nearest", "bilinear"]
 FLOAT_BAD = (-999.0, 999.0)  # fill values of the floating-point components: values that the data take
