@@ -8,10 +8,10 @@
 //   merge_overlay_kernel  steps 3 and 4 fused: a lane per target cell evaluates the inner->target entry on S and the outer->target
 //                         entry on O only where S does not reach
 // A lane owns one cell of a kTileX x kTileY tile and keeps its class (smoothing) or its plan entries (regrid) in registers over the
-// z loop; kAhead slices are in flight per lane.  Every slice has its own buffer descriptor, so a batch of any length is addressed
-// with 32-bit lane offsets (a slice holds fewer than 2^30 cells, plan.hpp).  The plan entries and the stencil arithmetic are those
-// of stencil_math.hpp, the cell classes and the blend those of merge_math.hpp.  Built with -ffp-contract=off: I + alpha * diff is a
-// multiply and an add, as in the reference.
+// z loop; kAhead slices are in flight per lane (tile, cell and z loop: merge_launch.hpp).  Every slice has its own buffer
+// descriptor, so a batch of any length is addressed with 32-bit lane offsets (a slice holds fewer than 2^30 cells, plan.hpp).  The
+// plan entries and the stencil arithmetic are those of stencil_math.hpp, the cell classes and the blend those of merge_math.hpp.
+// Built with -ffp-contract=off: I + alpha * diff is a multiply and an add, as in the reference.
 #include "gather_entry.hpp"
 #include "merge_launch.hpp"
 #include "merge_math.hpp"
@@ -23,14 +23,8 @@ namespace fimex_amd {
 
 namespace {
 
-using merge_launch::FloatScratch;
-using merge_launch::kAhead;
-using merge_launch::kTileX;
-using merge_launch::kTileY;
-using merge_launch::plan_ref;
-using merge_launch::PlanRef;
-using merge_launch::stencil_of;
-using merge_launch::tile_grid;
+using namespace merge_launch;
+using FloatPlan = PlanRef<float, 0>;
 
 // CDMBorderSmoothing_Linear::operator() on float interpolation arrays: the cell classes and the blend of merge_math.hpp
 using merge_math::SmoothClass;
@@ -45,36 +39,29 @@ __device__ __forceinline__ float smooth_value(const SmoothClass& c, float inner,
 struct SmoothArgs {
     const float *inner, *outer;  // [nz][ny][nx]
     float* out;
-    uint32_t nx, ny, nz, zPerBlock;
-    uint64_t tw, bw;
-    int useOuter;
+    Tile tile;
+    Smoothing sm;
 };
 
 // every lane reads its cell of both inputs before it writes it: out may be either of them
 __global__ void __launch_bounds__(kBlock) border_smooth_kernel(const SmoothArgs a)
 {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= a.nx || y >= a.ny) return;
-    const SmoothClass c = smooth_class(x, y, a.nx, a.ny, a.tw, a.bw);
-    const bool useOuter = a.useOuter != 0;
-    const size_t plane = (size_t)a.nx * a.ny;
-    const uint32_t planeBytes = (uint32_t)plane * 4u, cb = (y * a.nx + x) * 4u;
-    uint32_t z = blockIdx.z * a.zPerBlock;
-    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
-    for (; z + kAhead <= z1; z += kAhead) {
-        float vi[kAhead], vo[kAhead];
+    const Cell c(a.tile);
+    if (!c.inside) return;
+    const SmoothClass cls = smooth_class(c.x, c.y, a.tile.nx, a.tile.ny, a.sm.tw, a.sm.bw);
+    const bool useOuter = a.sm.useOuter != 0;
+    const uint32_t cb = c.offset<float>();
+    for_z_groups<kAhead>(c.z0, c.z1, [&](uint32_t z, auto n) {
+        constexpr int N = decltype(n)::value;
+        float vi[N], vo[N];
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) {
-            vi[k] = ld(make_rsrc(a.inner + (size_t)(z + k) * plane, planeBytes), cb);
-            vo[k] = ld(make_rsrc(a.outer + (size_t)(z + k) * plane, planeBytes), cb);
+        for (int k = 0; k < N; ++k) {
+            vi[k] = ld(c.slice(a.inner, z + k), cb);
+            vo[k] = ld(c.slice(a.outer, z + k), cb);
         }
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, 0, smooth_value(c, vi[k], vo[k], useOuter));
-    }
-    for (; z < z1; ++z) {
-        const float vi = ld(make_rsrc(a.inner + (size_t)z * plane, planeBytes), cb), vo = ld(make_rsrc(a.outer + (size_t)z * plane, planeBytes), cb);
-        st_plain(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, 0, smooth_value(c, vi, vo, useOuter));
-    }
+        for (int k = 0; k < N; ++k) st_plain(c.slice(a.out, z + k), cb, 0, smooth_value(cls, vi[k], vo[k], useOuter));
+    });
 }
 
 // CDMOverlay.cc:82-86.  A workgroup takes kAhead * kBlock consecutive values; a lane reads its values before it writes them.
@@ -96,53 +83,43 @@ __global__ void __launch_bounds__(kBlock) overlay_kernel(const float* top, const
 }
 
 struct MergeSmoothArgs {
-    PlanRef oi;           // outer -> inner grid
+    FloatPlan oi;         // outer -> inner grid
     const float *inner;   // [nz][ny][nx]
     const float *outer;   // [nz] source slices of oi
     float* s;             // [nz][ny][nx]
-    uint32_t nx, ny, nz, zPerBlock;
-    uint64_t tw, bw;
-    int useOuter;
+    Tile tile;
+    Smoothing sm;
 };
 
 // steps 1 and 2: S = smooth(I, regrid(O -> inner grid)), the regrid evaluated only where the smoothing reads it
 template <int STENCIL>
 __global__ void __launch_bounds__(kBlock) merge_smooth_kernel(const MergeSmoothArgs a)
 {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= a.nx || y >= a.ny) return;
-    const uint32_t cell = y * a.nx + x, cb = cell * 4u;
-    const SmoothClass c = smooth_class(x, y, a.nx, a.ny, a.tw, a.bw);
-    const GatherEntry<STENCIL, float> e = a.oi.entry<STENCIL>(cell);
-    const bool useOuter = a.useOuter != 0;
-    const size_t plane = (size_t)a.nx * a.ny;
-    const uint32_t planeBytes = (uint32_t)plane * 4u;
-    uint32_t z = blockIdx.z * a.zPerBlock;
-    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
-    for (; z + kAhead <= z1; z += kAhead) {
-        float vi[kAhead], vo[kAhead];
+    const Cell c(a.tile);
+    if (!c.inside) return;
+    const SmoothClass cls = smooth_class(c.x, c.y, a.tile.nx, a.tile.ny, a.sm.tw, a.sm.bw);
+    const GatherEntry<STENCIL, float> e = a.oi.entry<STENCIL>(c.cell);
+    const bool useOuter = a.sm.useOuter != 0;
+    const uint32_t cb = c.offset<float>();
+    for_z_groups<kAhead>(c.z0, c.z1, [&](uint32_t z, auto n) {
+        constexpr int N = decltype(n)::value;
+        float vi[N], vo[N];
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) vi[k] = ld(make_rsrc(a.inner + (size_t)(z + k) * plane, planeBytes), cb);
+        for (int k = 0; k < N; ++k) vi[k] = ld(c.slice(a.inner, z + k), cb);
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k)
-            vo[k] = needs_outer(c, vi[k], useOuter) ? e.value(make_rsrc(a.outer + (size_t)(z + k) * a.oi.inLayer, a.oi.inBytes)) : 0.f;
+        for (int k = 0; k < N; ++k) vo[k] = needs_outer(cls, vi[k], useOuter) ? e.value(a.oi.slice(a.outer, z + k)) : 0.f;
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) st_plain(make_rsrc(a.s + (size_t)(z + k) * plane, planeBytes), cb, 0, smooth_value(c, vi[k], vo[k], useOuter));
-    }
-    for (; z < z1; ++z) {
-        const float vi = ld(make_rsrc(a.inner + (size_t)z * plane, planeBytes), cb);
-        const float vo = needs_outer(c, vi, useOuter) ? e.value(make_rsrc(a.outer + (size_t)z * a.oi.inLayer, a.oi.inBytes)) : 0.f;
-        st_plain(make_rsrc(a.s + (size_t)z * plane, planeBytes), cb, 0, smooth_value(c, vi, vo, useOuter));
-    }
+        for (int k = 0; k < N; ++k) st_plain(c.slice(a.s, z + k), cb, 0, smooth_value(cls, vi[k], vo[k], useOuter));
+    });
 }
 
 struct MergeOverlayArgs {
-    PlanRef st;          // smoothed inner -> target
-    PlanRef ot;          // outer -> target
+    FloatPlan st;        // smoothed inner -> target
+    FloatPlan ot;        // outer -> target
     const float *s;      // [nz] source slices of st
     const float *outer;  // [nz] source slices of ot
     float* out;          // [nz][ny][nx]
-    uint32_t nx, ny, nz, zPerBlock;
+    Tile tile;
 };
 
 // steps 3 and 4: out = regrid(S -> target) where that is defined, else regrid(O -> target); an invalid inner -> target entry
@@ -150,39 +127,22 @@ struct MergeOverlayArgs {
 template <int ST, int OT>
 __global__ void __launch_bounds__(kBlock) merge_overlay_kernel(const MergeOverlayArgs a)
 {
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= a.nx || y >= a.ny) return;
-    const uint32_t cell = y * a.nx + x, cb = cell * 4u;
-    const GatherEntry<ST, float> es = a.st.entry<ST>(cell);
-    const GatherEntry<OT, float> eo = a.ot.entry<OT>(cell);
-    const size_t plane = (size_t)a.nx * a.ny;
-    const uint32_t planeBytes = (uint32_t)plane * 4u;
-    uint32_t z = blockIdx.z * a.zPerBlock;
-    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
-    for (; z + kAhead <= z1; z += kAhead) {
-        float v[kAhead];
+    const Cell c(a.tile);
+    if (!c.inside) return;
+    const GatherEntry<ST, float> es = a.st.entry<ST>(c.cell);
+    const GatherEntry<OT, float> eo = a.ot.entry<OT>(c.cell);
+    const uint32_t cb = c.offset<float>();
+    for_z_groups<kAhead>(c.z0, c.z1, [&](uint32_t z, auto n) {
+        constexpr int N = decltype(n)::value;
+        float v[N];
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) v[k] = es.value(make_rsrc(a.s + (size_t)(z + k) * a.st.inLayer, a.st.inBytes));
+        for (int k = 0; k < N; ++k) v[k] = es.value(a.st.slice(a.s, z + k));
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k)
-            if (v[k] != v[k]) v[k] = eo.value(make_rsrc(a.outer + (size_t)(z + k) * a.ot.inLayer, a.ot.inBytes));
+        for (int k = 0; k < N; ++k)
+            if (v[k] != v[k]) v[k] = eo.value(a.ot.slice(a.outer, z + k));
 #pragma unroll
-        for (int k = 0; k < kAhead; ++k) st_stream(make_rsrc(a.out + (size_t)(z + k) * plane, planeBytes), cb, 0, v[k]);
-    }
-    for (; z < z1; ++z) {
-        float v = es.value(make_rsrc(a.s + (size_t)z * a.st.inLayer, a.st.inBytes));
-        if (v != v) v = eo.value(make_rsrc(a.outer + (size_t)z * a.ot.inLayer, a.ot.inBytes));
-        st_stream(make_rsrc(a.out + (size_t)z * plane, planeBytes), cb, 0, v);
-    }
-}
-
-template <int ST>
-void launch_overlay_st(int ot, dim3 grid, const MergeOverlayArgs& a, hipStream_t stream)
-{
-    const dim3 block(kTileX, kTileY, 1);
-    if (ot == 1) merge_overlay_kernel<ST, 1><<<grid, block, 0, stream>>>(a);
-    else if (ot == 2) merge_overlay_kernel<ST, 2><<<grid, block, 0, stream>>>(a);
-    else merge_overlay_kernel<ST, 4><<<grid, block, 0, stream>>>(a);
+        for (int k = 0; k < N; ++k) st_stream(c.slice(a.out, z + k), cb, 0, v[k]);
+    });
 }
 
 }  // namespace
@@ -192,18 +152,9 @@ void launch_border_smooth(const float* d_inner, const float* d_outerOnInner, flo
                           size_t borderWidth, bool useOuter, hipStream_t stream)
 {
     if (nz == 0) return;
-    SmoothArgs a{};
-    const dim3 grid = tile_grid(nx, ny, nz, a.zPerBlock);
-    a.inner = d_inner;
-    a.outer = d_outerOnInner;
-    a.out = d_out;
-    a.nx = (uint32_t)nx;
-    a.ny = (uint32_t)ny;
-    a.nz = (uint32_t)nz;
-    a.tw = transitionWidth;
-    a.bw = borderWidth;
-    a.useOuter = useOuter ? 1 : 0;
-    border_smooth_kernel<<<grid, dim3(kTileX, kTileY, 1), 0, stream>>>(a);
+    SmoothArgs a{d_inner, d_outerOnInner, d_out, {}, smoothing(transitionWidth, borderWidth, useOuter)};
+    const dim3 grid = tile_grid(nx, ny, nz, a.tile);
+    border_smooth_kernel<<<grid, tile_block(), 0, stream>>>(a);
     FA_HIP(hipGetLastError());
 }
 
@@ -220,45 +171,18 @@ void launch_merge_fused(const fimex_amd_merge_plan& m, const float* d_inner, con
 {
     if (nz == 0) return;
     const fimex_amd_regrid_plan &oi = *m.outerToInner, &st = *m.innerToTarget, &ot = *m.outerToTarget;
-    const size_t innerCells = oi.outX * oi.outY;
-    FloatScratch s(nz * innerCells, stream);
-    const dim3 block(kTileX, kTileY, 1);
+    Scratch s(nz * oi.outX * oi.outY * sizeof(float), stream);
     {
-        MergeSmoothArgs a{};
-        const dim3 grid = tile_grid(oi.outX, oi.outY, nz, a.zPerBlock);
-        a.oi = plan_ref(oi);
-        a.inner = d_inner;
-        a.outer = d_outer;
-        a.s = s.get();
-        a.nx = (uint32_t)oi.outX;
-        a.ny = (uint32_t)oi.outY;
-        a.nz = (uint32_t)nz;
-        a.tw = m.transitionWidth;
-        a.bw = m.borderWidth;
-        a.useOuter = m.useOuter ? 1 : 0;
-        switch (stencil_of(oi)) {
-        case 1: merge_smooth_kernel<1><<<grid, block, 0, stream>>>(a); break;
-        case 2: merge_smooth_kernel<2><<<grid, block, 0, stream>>>(a); break;
-        default: merge_smooth_kernel<4><<<grid, block, 0, stream>>>(a); break;
-        }
+        MergeSmoothArgs a{plan_ref<float>(oi), d_inner, d_outer, s.get<float>(), {}, smoothing(m.transitionWidth, m.borderWidth, m.useOuter)};
+        const dim3 grid = tile_grid(oi.outX, oi.outY, nz, a.tile);
+        with_stencil(oi, [&](auto stencil) { merge_smooth_kernel<decltype(stencil)::value><<<grid, tile_block(), 0, stream>>>(a); });
         FA_HIP(hipGetLastError());
     }
-    MergeOverlayArgs a{};
-    const dim3 grid = tile_grid(st.outX, st.outY, nz, a.zPerBlock);
-    a.st = plan_ref(st);
-    a.ot = plan_ref(ot);
-    a.s = s.get();
-    a.outer = d_outer;
-    a.out = d_out;
-    a.nx = (uint32_t)st.outX;
-    a.ny = (uint32_t)st.outY;
-    a.nz = (uint32_t)nz;
-    const int otStencil = stencil_of(ot);
-    switch (stencil_of(st)) {
-    case 1: launch_overlay_st<1>(otStencil, grid, a, stream); break;
-    case 2: launch_overlay_st<2>(otStencil, grid, a, stream); break;
-    default: launch_overlay_st<4>(otStencil, grid, a, stream); break;
-    }
+    MergeOverlayArgs a{plan_ref<float>(st), plan_ref<float>(ot), s.get<float>(), d_outer, d_out, {}};
+    const dim3 grid = tile_grid(st.outX, st.outY, nz, a.tile);
+    with_stencil(st, [&](auto sts) {
+        with_stencil(ot, [&](auto ots) { merge_overlay_kernel<decltype(sts)::value, decltype(ots)::value><<<grid, tile_block(), 0, stream>>>(a); });
+    });
     FA_HIP(hipGetLastError());
 }
 
@@ -268,12 +192,13 @@ void launch_merge_chain(const fimex_amd_merge_plan& m, const float* d_inner, con
     if (nz == 0) return;
     const fimex_amd_regrid_plan &oi = *m.outerToInner, &st = *m.innerToTarget, &ot = *m.outerToTarget;
     const size_t innerCells = oi.outX * oi.outY, targetCells = st.outX * st.outY;
-    FloatScratch s(nz * innerCells, stream), top(nz * targetCells, stream);
-    apply_plan_device(oi, d_outer, nz, s.get(), stream);                                                               // step 1
-    launch_border_smooth(d_inner, s.get(), s.get(), oi.outX, oi.outY, nz, m.transitionWidth, m.borderWidth, m.useOuter, stream);  // step 2
-    apply_plan_device(st, s.get(), nz, top.get(), stream);                                                             // step 3
+    Scratch sBytes(nz * innerCells * sizeof(float), stream), topBytes(nz * targetCells * sizeof(float), stream);
+    float *s = sBytes.get<float>(), *top = topBytes.get<float>();
+    apply_plan_device(oi, d_outer, nz, s, stream);                                                               // step 1
+    launch_border_smooth(d_inner, s, s, oi.outX, oi.outY, nz, m.transitionWidth, m.borderWidth, m.useOuter, stream);  // step 2
+    apply_plan_device(st, s, nz, top, stream);                                                                   // step 3
     apply_plan_device(ot, d_outer, nz, d_out, stream);
-    launch_overlay(top.get(), d_out, d_out, nz * targetCells, stream);                                                 // step 4
+    launch_overlay(top, d_out, d_out, nz * targetCells, stream);                                                 // step 4
 }
 
 }  // namespace fimex_amd

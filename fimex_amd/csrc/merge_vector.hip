@@ -19,15 +19,8 @@ namespace fimex_amd {
 
 namespace {
 
-using merge_launch::ahead_of;
-using merge_launch::FloatScratch;
-using merge_launch::kTileX;
-using merge_launch::kTileY;
-using merge_launch::LazyMatrix;
-using merge_launch::plan_ref;
-using merge_launch::PlanRef;
-using merge_launch::stencil_of;
-using merge_launch::tile_grid;
+using namespace merge_launch;
+using FloatPlan = PlanRef<float, 0>;
 using merge_math::Pair;
 using merge_math::SmoothClass;
 
@@ -40,14 +33,13 @@ __device__ __forceinline__ Pair regrid_rotate(const GatherEntry<STENCIL, float>&
 }
 
 struct MergeSmoothVectorArgs {
-    PlanRef oi;                    // outer -> inner grid
+    FloatPlan oi;                  // outer -> inner grid
     const double2* rotOI;          // [ny][nx] (m0, m1) of R_oi
     const float *innerU, *innerV;  // [nz][ny][nx]
     const float *outerU, *outerV;  // [nz] source slices of oi
     float *su, *sv;                // [nz][ny][nx]
-    uint32_t nx, ny, nz, zPerBlock;
-    uint64_t tw, bw;
-    int useOuter;
+    Tile tile;
+    Smoothing sm;
 };
 
 // steps 1 and 2: (Su, Sv) = smooth((Iu, Iv), rot(R_oi; regrid(Ou), regrid(Ov))), the regrid and the rotation evaluated only
@@ -55,56 +47,43 @@ struct MergeSmoothVectorArgs {
 template <int STENCIL>
 __global__ void __launch_bounds__(kBlock) merge_smooth_vector_kernel(const MergeSmoothVectorArgs a)
 {
-    constexpr int AHEAD = ahead_of<STENCIL>();
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= a.nx || y >= a.ny) return;
-    const uint32_t cell = y * a.nx + x, cb = cell * 4u;
-    const SmoothClass c = merge_math::smooth_class(x, y, a.nx, a.ny, a.tw, a.bw);
-    const GatherEntry<STENCIL, float> e = a.oi.entry<STENCIL>(cell);
-    LazyMatrix rot{a.rotOI, cell};
-    const bool useOuter = a.useOuter != 0;
-    const size_t plane = (size_t)a.nx * a.ny;
-    const uint32_t planeBytes = (uint32_t)plane * 4u;
-    auto smooth = [&](uint32_t zz, float iu, float iv) {
-        return merge_math::smooth_pair(c, iu, iv, [&] {
-            return regrid_rotate<STENCIL>(e, make_rsrc(a.outerU + (size_t)zz * a.oi.inLayer, a.oi.inBytes),
-                                          make_rsrc(a.outerV + (size_t)zz * a.oi.inLayer, a.oi.inBytes), rot.get());
-        }, useOuter);
-    };
-    uint32_t z = blockIdx.z * a.zPerBlock;
-    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
-    for (; z + AHEAD <= z1; z += AHEAD) {
-        float iu[AHEAD], iv[AHEAD];
-        Pair s[AHEAD];
+    const Cell c(a.tile);
+    if (!c.inside) return;
+    const SmoothClass cls = merge_math::smooth_class(c.x, c.y, a.tile.nx, a.tile.ny, a.sm.tw, a.sm.bw);
+    const GatherEntry<STENCIL, float> e = a.oi.entry<STENCIL>(c.cell);
+    LazyMatrix rot{a.rotOI, c.cell};
+    const bool useOuter = a.sm.useOuter != 0;
+    const uint32_t cb = c.offset<float>();
+    for_z_groups<ahead_of<STENCIL>()>(c.z0, c.z1, [&](uint32_t z, auto n) {
+        constexpr int N = decltype(n)::value;
+        float iu[N], iv[N];
+        Pair s[N];
 #pragma unroll
-        for (int k = 0; k < AHEAD; ++k) {
-            iu[k] = ld(make_rsrc(a.innerU + (size_t)(z + k) * plane, planeBytes), cb);
-            iv[k] = ld(make_rsrc(a.innerV + (size_t)(z + k) * plane, planeBytes), cb);
+        for (int k = 0; k < N; ++k) {
+            iu[k] = ld(c.slice(a.innerU, z + k), cb);
+            iv[k] = ld(c.slice(a.innerV, z + k), cb);
         }
 #pragma unroll
-        for (int k = 0; k < AHEAD; ++k) s[k] = smooth(z + k, iu[k], iv[k]);
+        for (int k = 0; k < N; ++k)
+            s[k] = merge_math::smooth_pair(cls, iu[k], iv[k], [&] {
+                return regrid_rotate<STENCIL>(e, a.oi.slice(a.outerU, z + k), a.oi.slice(a.outerV, z + k), rot.get());
+            }, useOuter);
 #pragma unroll
-        for (int k = 0; k < AHEAD; ++k) {
-            st_plain(make_rsrc(a.su + (size_t)(z + k) * plane, planeBytes), cb, 0, s[k].u);
-            st_plain(make_rsrc(a.sv + (size_t)(z + k) * plane, planeBytes), cb, 0, s[k].v);
+        for (int k = 0; k < N; ++k) {
+            st_plain(c.slice(a.su, z + k), cb, 0, s[k].u);
+            st_plain(c.slice(a.sv, z + k), cb, 0, s[k].v);
         }
-    }
-    for (; z < z1; ++z) {
-        const float iu = ld(make_rsrc(a.innerU + (size_t)z * plane, planeBytes), cb), iv = ld(make_rsrc(a.innerV + (size_t)z * plane, planeBytes), cb);
-        const Pair s = smooth(z, iu, iv);
-        st_plain(make_rsrc(a.su + (size_t)z * plane, planeBytes), cb, 0, s.u);
-        st_plain(make_rsrc(a.sv + (size_t)z * plane, planeBytes), cb, 0, s.v);
-    }
+    });
 }
 
 struct MergeOverlayVectorArgs {
-    PlanRef st;                    // smoothed inner -> target
-    PlanRef ot;                    // outer -> target
+    FloatPlan st;                  // smoothed inner -> target
+    FloatPlan ot;                  // outer -> target
     const double2 *rotST, *rotOT;  // [ny][nx] (m0, m1) of R_st and R_ot
     const float *su, *sv;          // [nz] source slices of st
     const float *outerU, *outerV;  // [nz] source slices of ot
     float *outU, *outV;            // [nz][ny][nx]
-    uint32_t nx, ny, nz, zPerBlock;
+    Tile tile;
 };
 
 // steps 3 and 4: out = rot(R_st; regrid(Su), regrid(Sv)) where that is defined, component by component, else
@@ -112,54 +91,29 @@ struct MergeOverlayVectorArgs {
 template <int ST, int OT>
 __global__ void __launch_bounds__(kBlock) merge_overlay_vector_kernel(const MergeOverlayVectorArgs a)
 {
-    constexpr int AHEAD = ahead_of<(ST > OT ? ST : OT)>();
-    const uint32_t x = blockIdx.x * kTileX + threadIdx.x, y = blockIdx.y * kTileY + threadIdx.y;
-    if (x >= a.nx || y >= a.ny) return;
-    const uint32_t cell = y * a.nx + x, cb = cell * 4u;
-    const GatherEntry<ST, float> es = a.st.entry<ST>(cell);
-    const GatherEntry<OT, float> eo = a.ot.entry<OT>(cell);
-    const double2 mS = a.rotST[cell];
-    LazyMatrix rotO{a.rotOT, cell};
-    const size_t plane = (size_t)a.nx * a.ny;
-    const uint32_t planeBytes = (uint32_t)plane * 4u;
-    auto top = [&](uint32_t zz) {
-        return regrid_rotate<ST>(es, make_rsrc(a.su + (size_t)zz * a.st.inLayer, a.st.inBytes), make_rsrc(a.sv + (size_t)zz * a.st.inLayer, a.st.inBytes),
-                                 mS);
-    };
-    auto overlay = [&](uint32_t zz, const Pair& t) {
-        return merge_math::overlay_pair(t, [&] {
-            return regrid_rotate<OT>(eo, make_rsrc(a.outerU + (size_t)zz * a.ot.inLayer, a.ot.inBytes),
-                                     make_rsrc(a.outerV + (size_t)zz * a.ot.inLayer, a.ot.inBytes), rotO.get());
-        });
-    };
-    uint32_t z = blockIdx.z * a.zPerBlock;
-    const uint32_t z1 = min(a.nz, z + a.zPerBlock);
-    for (; z + AHEAD <= z1; z += AHEAD) {
-        Pair p[AHEAD];
+    const Cell c(a.tile);
+    if (!c.inside) return;
+    const GatherEntry<ST, float> es = a.st.entry<ST>(c.cell);
+    const GatherEntry<OT, float> eo = a.ot.entry<OT>(c.cell);
+    const double2 mS = a.rotST[c.cell];
+    LazyMatrix rotO{a.rotOT, c.cell};
+    const uint32_t cb = c.offset<float>();
+    for_z_groups<ahead_of<(ST > OT ? ST : OT)>()>(c.z0, c.z1, [&](uint32_t z, auto n) {
+        constexpr int N = decltype(n)::value;
+        Pair p[N];
 #pragma unroll
-        for (int k = 0; k < AHEAD; ++k) p[k] = top(z + k);
+        for (int k = 0; k < N; ++k) p[k] = regrid_rotate<ST>(es, a.st.slice(a.su, z + k), a.st.slice(a.sv, z + k), mS);
 #pragma unroll
-        for (int k = 0; k < AHEAD; ++k) p[k] = overlay(z + k, p[k]);
+        for (int k = 0; k < N; ++k)
+            p[k] = merge_math::overlay_pair(p[k], [&] {
+                return regrid_rotate<OT>(eo, a.ot.slice(a.outerU, z + k), a.ot.slice(a.outerV, z + k), rotO.get());
+            });
 #pragma unroll
-        for (int k = 0; k < AHEAD; ++k) {
-            st_stream(make_rsrc(a.outU + (size_t)(z + k) * plane, planeBytes), cb, 0, p[k].u);
-            st_stream(make_rsrc(a.outV + (size_t)(z + k) * plane, planeBytes), cb, 0, p[k].v);
+        for (int k = 0; k < N; ++k) {
+            st_stream(c.slice(a.outU, z + k), cb, 0, p[k].u);
+            st_stream(c.slice(a.outV, z + k), cb, 0, p[k].v);
         }
-    }
-    for (; z < z1; ++z) {
-        const Pair p = overlay(z, top(z));
-        st_stream(make_rsrc(a.outU + (size_t)z * plane, planeBytes), cb, 0, p.u);
-        st_stream(make_rsrc(a.outV + (size_t)z * plane, planeBytes), cb, 0, p.v);
-    }
-}
-
-template <int ST>
-void launch_overlay_st(int ot, dim3 grid, const MergeOverlayVectorArgs& a, hipStream_t stream)
-{
-    const dim3 block(kTileX, kTileY, 1);
-    if (ot == 1) merge_overlay_vector_kernel<ST, 1><<<grid, block, 0, stream>>>(a);
-    else if (ot == 2) merge_overlay_vector_kernel<ST, 2><<<grid, block, 0, stream>>>(a);
-    else merge_overlay_vector_kernel<ST, 4><<<grid, block, 0, stream>>>(a);
+    });
 }
 
 }  // namespace
@@ -171,55 +125,21 @@ void launch_merge_vector_fused(const fimex_amd_merge_plan& m, const fimex_amd_ve
 {
     if (nz == 0) return;
     const fimex_amd_regrid_plan &oi = *m.outerToInner, &st = *m.innerToTarget, &ot = *m.outerToTarget;
-    const size_t innerCells = oi.outX * oi.outY;
-    FloatScratch s(2 * nz * innerCells, stream);  // Su, then Sv
-    float *su = s.get(), *sv = s.get() + nz * innerCells;
-    const dim3 block(kTileX, kTileY, 1);
+    const size_t innerN = nz * oi.outX * oi.outY;
+    Scratch s(2 * innerN * sizeof(float), stream);  // Su, then Sv
+    float *su = s.get<float>(), *sv = su + innerN;
     {
-        MergeSmoothVectorArgs a{};
-        const dim3 grid = tile_grid(oi.outX, oi.outY, nz, a.zPerBlock);
-        a.oi = plan_ref(oi);
-        a.rotOI = rotOI.cossin.get();
-        a.innerU = d_innerU;
-        a.innerV = d_innerV;
-        a.outerU = d_outerU;
-        a.outerV = d_outerV;
-        a.su = su;
-        a.sv = sv;
-        a.nx = (uint32_t)oi.outX;
-        a.ny = (uint32_t)oi.outY;
-        a.nz = (uint32_t)nz;
-        a.tw = m.transitionWidth;
-        a.bw = m.borderWidth;
-        a.useOuter = m.useOuter ? 1 : 0;
-        switch (stencil_of(oi)) {
-        case 1: merge_smooth_vector_kernel<1><<<grid, block, 0, stream>>>(a); break;
-        case 2: merge_smooth_vector_kernel<2><<<grid, block, 0, stream>>>(a); break;
-        default: merge_smooth_vector_kernel<4><<<grid, block, 0, stream>>>(a); break;
-        }
+        MergeSmoothVectorArgs a{plan_ref<float>(oi), rotOI.cossin.get(), d_innerU, d_innerV, d_outerU, d_outerV, su, sv, {},
+                                smoothing(m.transitionWidth, m.borderWidth, m.useOuter)};
+        const dim3 grid = tile_grid(oi.outX, oi.outY, nz, a.tile);
+        with_stencil(oi, [&](auto stencil) { merge_smooth_vector_kernel<decltype(stencil)::value><<<grid, tile_block(), 0, stream>>>(a); });
         FA_HIP(hipGetLastError());
     }
-    MergeOverlayVectorArgs a{};
-    const dim3 grid = tile_grid(st.outX, st.outY, nz, a.zPerBlock);
-    a.st = plan_ref(st);
-    a.ot = plan_ref(ot);
-    a.rotST = rotST.cossin.get();
-    a.rotOT = rotOT.cossin.get();
-    a.su = su;
-    a.sv = sv;
-    a.outerU = d_outerU;
-    a.outerV = d_outerV;
-    a.outU = d_outU;
-    a.outV = d_outV;
-    a.nx = (uint32_t)st.outX;
-    a.ny = (uint32_t)st.outY;
-    a.nz = (uint32_t)nz;
-    const int otStencil = stencil_of(ot);
-    switch (stencil_of(st)) {
-    case 1: launch_overlay_st<1>(otStencil, grid, a, stream); break;
-    case 2: launch_overlay_st<2>(otStencil, grid, a, stream); break;
-    default: launch_overlay_st<4>(otStencil, grid, a, stream); break;
-    }
+    MergeOverlayVectorArgs a{plan_ref<float>(st), plan_ref<float>(ot), rotST.cossin.get(), rotOT.cossin.get(), su, sv, d_outerU, d_outerV, d_outU, d_outV, {}};
+    const dim3 grid = tile_grid(st.outX, st.outY, nz, a.tile);
+    with_stencil(st, [&](auto sts) {
+        with_stencil(ot, [&](auto ots) { merge_overlay_vector_kernel<decltype(sts)::value, decltype(ots)::value><<<grid, tile_block(), 0, stream>>>(a); });
+    });
     FA_HIP(hipGetLastError());
 }
 
@@ -232,8 +152,8 @@ void launch_merge_vector_chain(const fimex_amd_merge_plan& m, const fimex_amd_ve
     if (nz == 0) return;
     const fimex_amd_regrid_plan &oi = *m.outerToInner, &st = *m.innerToTarget, &ot = *m.outerToTarget;
     const size_t innerN = nz * oi.outX * oi.outY, targetN = nz * st.outX * st.outY;
-    FloatScratch s(2 * innerN, stream), top(2 * targetN, stream);
-    float *su = s.get(), *sv = s.get() + innerN, *topU = top.get(), *topV = top.get() + targetN;
+    Scratch s(2 * innerN * sizeof(float), stream), top(2 * targetN * sizeof(float), stream);
+    float *su = s.get<float>(), *sv = su + innerN, *topU = top.get<float>(), *topV = topU + targetN;
     apply_vector_pair(oi, rotOI, d_outerU, d_outerV, nz, su, sv, stream);                                                    // step 1
     launch_border_smooth(d_innerU, su, su, oi.outX, oi.outY, nz, m.transitionWidth, m.borderWidth, m.useOuter, stream);       // step 2
     launch_border_smooth(d_innerV, sv, sv, oi.outX, oi.outY, nz, m.transitionWidth, m.borderWidth, m.useOuter, stream);

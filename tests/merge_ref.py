@@ -208,9 +208,10 @@ def merge_positions(inner, outer, target, **kw):
     return positions(outer, inner, **kw), positions(inner, target, **kw), positions(outer, target, **kw)
 
 
-def merge(I, O, pos, shapes, method=oracle.BILINEAR, smooth_method=oracle.BILINEAR, tw=5, bw=2, use_outer=True):
+def merge(I, O, pos, shapes, method=oracle.BILINEAR, smooth_method=oracle.BILINEAR, tw=5, bw=2, use_outer=True, outer_method=None):
     """CDMMerger::getDataSlice on float fields I [nz][iy][ix] and O [nz][oy][ox].  pos: merge_positions' three pairs; shapes:
-    ((iy, ix), (oy, ox), (ty, tx)).  -> (out [nz][ty][tx], the smoothed inner field S)"""
+    ((iy, ix), (oy, ox), (ty, tx)); outer_method: the method of the outer -> target regrid where it is not `method` (the reference
+    gives both one, the library's merge plan takes any two backward plans).  -> (out [nz][ty][tx], the smoothed inner field S)"""
     (iy, ix), (oy, ox), (ty, tx) = shapes
     (oi_x, oi_y), (it_x, it_y), (ot_x, ot_y) = pos
     I = np.asarray(I, np.float32).reshape(-1, iy, ix)
@@ -218,7 +219,7 @@ def merge(I, O, pos, shapes, method=oracle.BILINEAR, smooth_method=oracle.BILINE
     OI = oracle.interpolate_values(smooth_method, oi_x, oi_y, O, ox, oy, ix, iy)  # step 1 (CDMBorderSmoothing's interpolator)
     S = border_smooth(I, OI, tw, bw, use_outer)                                   # step 2
     ST = oracle.interpolate_values(method, it_x, it_y, S, ix, iy, tx, ty)         # step 3
-    OT = oracle.interpolate_values(method, ot_x, ot_y, O, ox, oy, tx, ty)
+    OT = oracle.interpolate_values(method if outer_method is None else outer_method, ot_x, ot_y, O, ox, oy, tx, ty)
     return overlay(ST, OT), S                                                     # step 4
 
 

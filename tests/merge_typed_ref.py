@@ -88,9 +88,9 @@ def overlay_typed(top, pt, base, pb):
 Merged = collections.namedtuple("Merged", "out S branch OI OI_float ST OT OT_float")
 
 
-def merge_typed(I, pi, O, po, pos, shapes, method=oracle.BILINEAR, smooth_method=oracle.BILINEAR, tw=5, bw=2, use_outer=True):
+def merge_typed(I, pi, O, po, pos, shapes, method=oracle.BILINEAR, smooth_method=oracle.BILINEAR, tw=5, bw=2, use_outer=True, outer_method=None):
     """steps 1-4 on I [nz][iy][ix] in packing pi and O [nz][oy][ox] in packing po.  pos: merge_ref.merge_positions' three pairs;
-    shapes: ((iy, ix), (oy, ox), (ty, tx))."""
+    shapes: ((iy, ix), (oy, ox), (ty, tx)); outer_method: the method of the outer -> target regrid where it is not `method`."""
     (iy, ix), (oy, ox), (ty, tx) = shapes
     (oi_x, oi_y), (it_x, it_y), (ot_x, ot_y) = pos
     I = np.ascontiguousarray(I, dtype_of(pi)).reshape(-1, iy, ix)
@@ -98,7 +98,7 @@ def merge_typed(I, pi, O, po, pos, shapes, method=oracle.BILINEAR, smooth_method
     OI, OI_float = regrid_typed(smooth_method, oi_x, oi_y, O, po, ox, oy, ix, iy)  # step 1
     S, branch = smooth_typed(I, pi, OI, po, tw, bw, use_outer)                      # step 2
     ST, _ = regrid_typed(method, it_x, it_y, S, pi, ix, iy, tx, ty)                 # step 3
-    OT, OT_float = regrid_typed(method, ot_x, ot_y, O, po, ox, oy, tx, ty)
+    OT, OT_float = regrid_typed(method if outer_method is None else outer_method, ot_x, ot_y, O, po, ox, oy, tx, ty)
     return Merged(overlay_typed(ST, pi, OT, po), S, branch, OI, OI_float, ST, OT, OT_float)  # step 4
 
 

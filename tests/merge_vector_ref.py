@@ -37,9 +37,11 @@ def regrid_rotate(method, pos, u, v, src_shape, dst_shape, matrix):
     return oracle.vector_reproject_values(matrix, ru, rv, dx, dy)
 
 
-def merge_vector(Iu, Iv, Ou, Ov, pos, shapes, matrices, method=oracle.BILINEAR, smooth_method=oracle.BILINEAR, tw=5, bw=2, use_outer=True):
+def merge_vector(Iu, Iv, Ou, Ov, pos, shapes, matrices, method=oracle.BILINEAR, smooth_method=oracle.BILINEAR, tw=5, bw=2, use_outer=True,
+                 outer_method=None):
     """pos: merge_ref.merge_positions' three pairs; shapes: ((iy, ix), (oy, ox), (ty, tx)); matrices: (R_oi on the inner grid, R_st
-    and R_ot on the target), each the reference's double[4 * cells].  -> (outU, outV, Su, Sv)"""
+    and R_ot on the target), each the reference's double[4 * cells]; outer_method: the method of the outer -> target regrid where it
+    is not `method`.  -> (outU, outV, Su, Sv)"""
     inner, outer, target = shapes
     p_oi, p_st, p_ot = pos
     R_oi, R_st, R_ot = matrices
@@ -48,5 +50,5 @@ def merge_vector(Iu, Iv, Ou, Ov, pos, shapes, matrices, method=oracle.BILINEAR, 
     OIu, OIv = regrid_rotate(smooth_method, p_oi, Ou, Ov, outer, inner, R_oi)                               # step 1
     Su, Sv = mr.border_smooth(Iu, OIu, tw, bw, use_outer), mr.border_smooth(Iv, OIv, tw, bw, use_outer)     # step 2
     STu, STv = regrid_rotate(method, p_st, Su, Sv, inner, target, R_st)                                     # step 3
-    OTu, OTv = regrid_rotate(method, p_ot, Ou, Ov, outer, target, R_ot)
+    OTu, OTv = regrid_rotate(method if outer_method is None else outer_method, p_ot, Ou, Ov, outer, target, R_ot)
     return mr.overlay(STu, OTu), mr.overlay(STv, OTv), Su, Sv                                               # step 4

@@ -37,9 +37,10 @@ MergedPair = collections.namedtuple("MergedPair", "outU outV Su Sv branchU branc
 
 
 def merge_vector_typed(Iu, pIu, Iv, pIv, Ou, pOu, Ov, pOv, pos, shapes, matrices, method=oracle.BILINEAR, smooth_method=oracle.BILINEAR, tw=5,
-                       bw=2, use_outer=True):
+                       bw=2, use_outer=True, outer_method=None):
     """steps 1-4.  pos: merge_ref.merge_positions' three pairs; shapes: ((iy, ix), (oy, ox), (ty, tx)); matrices: (R_oi on the inner
-    grid, R_st and R_ot on the target), each the reference's double[4 * cells].  outU has inner u's type and packing, outV inner
+    grid, R_st and R_ot on the target), each the reference's double[4 * cells]; outer_method: the method of the outer -> target regrid where it is not
+    `method`.  outU has inner u's type and packing, outV inner
     v's; the *_float members are the rotated float pairs of the three regrids, in front of their roundings."""
     inner, outer, target = (tuple(s) for s in shapes)
     p_oi, p_st, p_ot = pos
@@ -52,7 +53,7 @@ def merge_vector_typed(Iu, pIu, Iv, pIv, Ou, pOu, Ov, pOv, pos, shapes, matrices
     Su, branchU = mt.smooth_typed(Iu, pIu, OIu, pOu, tw, bw, use_outer)                                    # step 2
     Sv, branchV = mt.smooth_typed(Iv, pIv, OIv, pOv, tw, bw, use_outer)
     STu, STv, ST_float = regrid_rotate_typed(method, p_st, Su, pIu, Sv, pIv, inner, target, R_st)          # step 3
-    OTu, OTv, OT_float = regrid_rotate_typed(method, p_ot, Ou, pOu, Ov, pOv, outer, target, R_ot)
+    OTu, OTv, OT_float = regrid_rotate_typed(method if outer_method is None else outer_method, p_ot, Ou, pOu, Ov, pOv, outer, target, R_ot)
     return MergedPair(mt.overlay_typed(STu, pIu, OTu, pOu), mt.overlay_typed(STv, pIv, OTv, pOv), Su, Sv, branchU, branchV, OI_float, ST_float,
                       OT_float)                                                                             # step 4
 
