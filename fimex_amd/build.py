@@ -32,6 +32,10 @@ MERGE_VECTOR_MATH_LIB = os.path.join(HERE, "libmerge_vector_math_host.so")  # cs
 MERGE_VECTOR_MATH_SHIM = os.path.join(ROOT, "tests", "merge_vector_math_host.cc")
 MERGE_VECTOR_TYPED_MATH_LIB = os.path.join(HERE, "libmerge_vector_typed_math_host.so")  # csrc/merge_vector_typed_math.hpp compiled for the CPU with g++ (tests/test_merge_vector_typed_math_host.py)
 MERGE_VECTOR_TYPED_MATH_SHIM = os.path.join(ROOT, "tests", "merge_vector_typed_math_host.cc")
+BLEND_MATH_LIB = os.path.join(HERE, "libblend_math_host.so")  # csrc/blend_math.hpp compiled for the CPU with g++ (tests/test_blend_math_host.py)
+BLEND_MATH_SHIM = os.path.join(ROOT, "tests", "blend_math_host.cc")
+VERTICAL_SEARCH_LIB = os.path.join(HERE, "libvertical_search_host.so")  # csrc/vertical_search.hpp compiled for the CPU (tests/test_vertical_search_host.py)
+VERTICAL_SEARCH_SHIM = os.path.join(ROOT, "tests", "vertical_search_host.hip")
 
 DEVICE_SOURCES = ["capi.hip", "capi_regrid.hip", "capi_regrid_multi.hip", "capi_vector.hip", "capi_fill.hip", "capi_vertical.hip", "capi_vertical_plan.hip", "capi_merge.hip", "capi_merge_typed.hip", "capi_merge_vector.hip", "capi_merge_vector_typed.hip", "capi_derived.hip", "capi_time_quality.hip", "capi_extract.hip", "backward_plan.hip", "gather.hip", "staged.hip", "staged2_plan.hip", "staged2.hip", "staged2_typed.hip", "staged2_vector.hip", "staged2_vector_typed.hip", "staged2_list.hip", "staged2_list_typed.hip", "forward_plan.hip", "forward.hip", "forward_median.hip", "forward_tiled.hip", "vector.hip", "convert.hip", "fill_sum.hip", "fill_prologue.hip", "fill.hip", "creepfill.hip", "fill_rects.hip", "projection_parse.hip", "projection.hip", "coordsearch.hip", "hostpipe.hip", "batch.hip", "vertical.hip", "vertical_levels.hip", "vertical_velocity.hip", "merge.hip", "merge_typed.hip", "merge_vector.hip", "merge_vector_typed.hip", "scaled_convert.hip", "pressure_convert.hip",
                   "time_accumulate.hip", "time_interpolate.hip", "quality.hip", "extract.hip", "vertical_plan.hip"]
@@ -115,90 +119,72 @@ def build_host(force=False):
     return HOSTLIB
 
 
-def build_stencil_host(force=False):
-    """The backward stencil rules the kernels compile (csrc/stencil_math.hpp), for the host only: the tests run it on the CPU, without a GPU."""
-    if force or _newer(STENCIL_LIB, [STENCIL_SHIM] + _headers()):
-        cmd = [_hipcc(), "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC,
-               STENCIL_SHIM, "-o", STENCIL_LIB, "-Wl,-rpath,/opt/rocm/lib"]
+def _build_shim(what, compiler, sources, deps, out, force):
+    """One host-only shared library of a shim under tests/ and the header it compiles: compiler "hipcc" (--cuda-host-only, for
+    headers that need HIP's) or "g++" (no HIP header at all).  deps: what a newer file of rebuilds it, besides the sources."""
+    if force or _newer(out, sources + deps):
+        front = [_hipcc(), "--cuda-host-only", "-Wno-unused-function"] if compiler == "hipcc" else ["g++"]
+        back = ["-Wl,-rpath,/opt/rocm/lib"] if compiler == "hipcc" else []
+        cmd = front + ["-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC] + sources + ["-o", out] + back
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
-            raise RuntimeError("stencil shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
+            raise RuntimeError("%s shim build failed:\n%s\n%s" % (what, r.stdout, r.stderr))
         if r.stderr.strip():
             sys.stderr.write(r.stderr)
-    return STENCIL_LIB
+    return out
+
+
+def _csrc(*names):
+    return [os.path.join(CSRC, n) for n in names]
+
+
+def build_stencil_host(force=False):
+    """The backward stencil rules the kernels compile (csrc/stencil_math.hpp), for the host only: the tests run it on the CPU, without a GPU."""
+    return _build_shim("stencil", "hipcc", [STENCIL_SHIM], _headers(), STENCIL_LIB, force)
 
 
 def build_projection_host(force=False):
     """The projections' point math (csrc/proj_math.hpp) and the PROJ.4 string parser, for the host only: the tests run them on the CPU."""
-    parse = os.path.join(CSRC, "projection_parse.hip")
-    if force or _newer(PROJECTION_LIB, [PROJECTION_SHIM, parse] + _headers()):
-        cmd = [_hipcc(), "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC,
-               PROJECTION_SHIM, parse, "-o", PROJECTION_LIB, "-Wl,-rpath,/opt/rocm/lib"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("projection shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
-        if r.stderr.strip():
-            sys.stderr.write(r.stderr)
-    return PROJECTION_LIB
+    return _build_shim("projection", "hipcc", [PROJECTION_SHIM] + _csrc("projection_parse.hip"), _headers(), PROJECTION_LIB, force)
 
 
 def build_forward_math_host(force=False):
     """The forward aggregation rules the kernels compile (csrc/forward_math.hpp), for the host only: the tests run them on the CPU."""
-    if force or _newer(FORWARD_MATH_LIB, [FORWARD_MATH_SHIM] + _headers()):
-        cmd = [_hipcc(), "--cuda-host-only", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC,
-               FORWARD_MATH_SHIM, "-o", FORWARD_MATH_LIB, "-Wl,-rpath,/opt/rocm/lib"]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("forward math shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
-        if r.stderr.strip():
-            sys.stderr.write(r.stderr)
-    return FORWARD_MATH_LIB
+    return _build_shim("forward math", "hipcc", [FORWARD_MATH_SHIM], _headers(), FORWARD_MATH_LIB, force)
 
 
 def build_merge_math_host(force=False):
     """The merge's per-cell arithmetic the kernels compile (csrc/merge_math.hpp), with g++ and no HIP header: the tests run it on the CPU."""
-    if force or _newer(MERGE_MATH_LIB, [MERGE_MATH_SHIM, os.path.join(CSRC, "merge_math.hpp")]):
-        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC, MERGE_MATH_SHIM, "-o", MERGE_MATH_LIB]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("merge math shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
-        if r.stderr.strip():
-            sys.stderr.write(r.stderr)
-    return MERGE_MATH_LIB
+    return _build_shim("merge math", "g++", [MERGE_MATH_SHIM], _csrc("merge_math.hpp"), MERGE_MATH_LIB, force)
 
 
 def build_merge_vector_math_host(force=False):
     """The merge's per-cell arithmetic on a vector pair (csrc/merge_vector_math.hpp), with g++ and no HIP header: the tests run it on the CPU."""
-    deps = [MERGE_VECTOR_MATH_SHIM, os.path.join(CSRC, "merge_vector_math.hpp"), os.path.join(CSRC, "merge_math.hpp")]
-    if force or _newer(MERGE_VECTOR_MATH_LIB, deps):
-        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC, MERGE_VECTOR_MATH_SHIM, "-o",
-               MERGE_VECTOR_MATH_LIB]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("merge vector math shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
-        if r.stderr.strip():
-            sys.stderr.write(r.stderr)
-    return MERGE_VECTOR_MATH_LIB
+    return _build_shim("merge vector math", "g++", [MERGE_VECTOR_MATH_SHIM], _csrc("merge_vector_math.hpp", "merge_math.hpp"), MERGE_VECTOR_MATH_LIB, force)
 
 
 def build_merge_vector_typed_math_host(force=False):
     """The merge's per-cell arithmetic on a vector pair in its stored types (csrc/merge_vector_typed_math.hpp), with g++ and no HIP header: the tests run it on the CPU."""
-    deps = [MERGE_VECTOR_TYPED_MATH_SHIM] + [os.path.join(CSRC, h) for h in ("merge_vector_typed_math.hpp", "merge_vector_math.hpp", "merge_math.hpp")]
-    if force or _newer(MERGE_VECTOR_TYPED_MATH_LIB, deps):
-        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-I" + CSRC, MERGE_VECTOR_TYPED_MATH_SHIM, "-o",
-               MERGE_VECTOR_TYPED_MATH_LIB]
-        r = subprocess.run(cmd, capture_output=True, text=True)
-        if r.returncode != 0:
-            raise RuntimeError("merge vector typed math shim build failed:\n%s\n%s" % (r.stdout, r.stderr))
-        if r.stderr.strip():
-            sys.stderr.write(r.stderr)
-    return MERGE_VECTOR_TYPED_MATH_LIB
+    return _build_shim("merge vector typed math", "g++", [MERGE_VECTOR_TYPED_MATH_SHIM],
+                       _csrc("merge_vector_typed_math.hpp", "merge_vector_math.hpp", "merge_math.hpp"), MERGE_VECTOR_TYPED_MATH_LIB, force)
+
+
+def build_blend_math_host(force=False):
+    """The 1-D blends the kernels and the host entries compile (csrc/blend_math.hpp), with g++ and no HIP header: the tests run them on the CPU."""
+    return _build_shim("blend math", "g++", [BLEND_MATH_SHIM], _csrc("blend_math.hpp") + [os.path.join(ROOT, "include", "fimex_amd.h")],
+                       BLEND_MATH_LIB, force)
+
+
+def build_vertical_search_host(force=False):
+    """The level search of the vertical kernels (csrc/vertical_search.hpp), for the host only: the tests run it on the CPU."""
+    return _build_shim("vertical search", "hipcc", [VERTICAL_SEARCH_SHIM], _headers(), VERTICAL_SEARCH_LIB, force)
 
 
 def clean():
     """Removes every built artefact, so that the next build starts from the sources alone."""
     shutil.rmtree(OBJ, ignore_errors=True)
-    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, STENCIL_LIB, PROJECTION_LIB, FORWARD_MATH_LIB, MERGE_MATH_LIB, MERGE_VECTOR_MATH_LIB, MERGE_VECTOR_TYPED_MATH_LIB, os.path.join(HERE, "host_cli.so")):
+    for f in (LIB, TUNING_LIB, HOSTLIB, HOSTCLI, STENCIL_LIB, PROJECTION_LIB, FORWARD_MATH_LIB, MERGE_MATH_LIB, MERGE_VECTOR_MATH_LIB, MERGE_VECTOR_TYPED_MATH_LIB, BLEND_MATH_LIB, VERTICAL_SEARCH_LIB,
+              os.path.join(HERE, "host_cli.so")):
         if os.path.exists(f):
             os.remove(f)
 
@@ -215,6 +201,8 @@ def build_all(force=False, jobs=4):
     build_merge_math_host(force=force)
     build_merge_vector_math_host(force=force)
     build_merge_vector_typed_math_host(force=force)
+    build_blend_math_host(force=force)
+    build_vertical_search_host(force=force)
     return lib, host
 
 

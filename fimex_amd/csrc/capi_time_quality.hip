@@ -41,15 +41,11 @@ void time_mapping(const double* oldTimes, size_t nOld, const double* newTimes, s
     }
 }
 
-// f and the branch of mifi_get_values_linear_conf_extrapol_f(-1, 2, ...) it selects, src/interpolation.c:1087-1102
+// f and the branch of mifi_get_values_linear_weak_extrapol_f it selects (blend_math.hpp)
 TimeStep time_step(size_t t1, size_t t2, double a, double b, double x)
 {
-    const float f = (a == b) ? 0 : ((x - a) / (b - a));
-    TimeStepClass cls = TimeStepClass::Undefined;
-    if (f == 0) cls = TimeStepClass::CopyA;
-    else if (f == 1) cls = TimeStepClass::CopyB;
-    else if ((f >= -1.f) && (f <= 2.f)) cls = TimeStepClass::Blend;
-    return TimeStep{(uint32_t)t1, (uint32_t)t2, f, cls};
+    const blend_math::Blend c = blend_math::classify(blend_math::kLinearWeakExtrapol, a, b, x);
+    return TimeStep{(uint32_t)t1, (uint32_t)t2, c.f, c.cls};
 }
 
 template <class Call>

@@ -13,17 +13,7 @@ namespace {
 bool check_vertical_call(int method, size_t nx, size_t ny, size_t nt, const void* in, const fimex_amd_vertical_levels* inLevels,
                          const fimex_amd_vertical_levels* outLevels, const double* level1, size_t nzo, const void* out)
 {
-    FA_REQUIRE(vertical_method_known(method), "unknown vertical interpolation method " + std::to_string(method));
-    const bool nonEmpty = nx * ny * nt > 0;
-    check_vertical_levels(inLevels, "input", nonEmpty);
-    if (outLevels) {
-        check_vertical_levels(outLevels, "template", nonEmpty);
-        FA_REQUIRE(outLevels->nz == nzo, "nzo differs from the template's number of levels");
-    }
-    if (!nonEmpty) return false;
-    FA_REQUIRE(outLevels != nullptr || level1 != nullptr, "fixed levels need level1[nzo]");
-    FA_REQUIRE(inLevels->nz > 0, "no input levels (nzi == 0)");
-    FA_REQUIRE(nzo > 0, "no output levels (nzo == 0)");
+    if (!check_vertical_search(method, nx, ny, nt, inLevels, outLevels, level1, nzo, true)) return false;
     FA_REQUIRE(in != nullptr && out != nullptr, "NULL data buffer");
     const char *i0 = static_cast<const char*>(in), *o0 = static_cast<const char*>(out);
     const size_t cells = nx * ny * nt * sizeof(float);

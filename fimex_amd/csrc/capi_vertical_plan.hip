@@ -23,16 +23,7 @@ void plan_create(Call&& c, int method, size_t nx, size_t ny, size_t nt, const fi
 {
     FA_REQUIRE(plan != nullptr, "NULL argument");
     *plan = nullptr;
-    FA_REQUIRE(vertical_method_known(method), "unknown vertical interpolation method " + std::to_string(method));
-    const bool nonEmpty = nx * ny * nt > 0;
-    check_vertical_levels(inLevels, "input", nonEmpty);
-    if (outLevels) {
-        check_vertical_levels(outLevels, "template", nonEmpty);
-        FA_REQUIRE(outLevels->nz == nzo, "nzo differs from the template's number of levels");
-    }
-    FA_REQUIRE(outLevels != nullptr || level1 != nullptr, "fixed levels need level1[nzo]");
-    FA_REQUIRE(inLevels->nz > 0, "no input levels (nzi == 0)");
-    FA_REQUIRE(nzo > 0, "no output levels (nzo == 0)");
+    (void)check_vertical_search(method, nx, ny, nt, inLevels, outLevels, level1, nzo, false);  // differs: asks on an empty grid too
     FA_REQUIRE(inLevels->nz <= kMaxInputLevels, "a plan holds level indices in 16 bits: at most 65535 input levels (nzi > 65535)");
     FA_REQUIRE(nt <= 65535, "at most 65535 unlimited-dimension positions per plan");
     size_t plane = 0, cells = 0, entries = 0, bytes = 0;

@@ -2,6 +2,7 @@
 //
 // Replaces mifi_bad2nanf / mifi_nanf2bad (src/interpolation.c:1775-1793) and
 // mifi_points2position (src/interpolation.c:104-217).
+#include "blend_math.hpp"
 #include "plan.hpp"
 #include "typed_convert.hpp"
 
@@ -235,76 +236,41 @@ void copy_field(const T* src, T* dst, size_t n, hipStream_t stream)  // the refe
     if (src != dst) FA_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, stream));
 }
 
+// one branch of blend_math.hpp's classify on whole fields: the reference's memcpy, its loop (:1041-1046, :1075-1080) or its
+// fill with MIFI_UNDEFINED_F (:1097-1101)
 template <typename T>
-void blend(const T* A, const T* B, T* out, size_t n, T f, hipStream_t stream)
+void blend_fields(blend_math::Class cls, T f, const T* A, const T* B, T* out, size_t n, hipStream_t stream)
 {
-    blend_kernel<T><<<stream_blocks(n), kBlock, 0, stream>>>(A, B, out, n, f);
-    FA_HIP(hipGetLastError());
-}
-
-// mifi_get_values_linear_f, :1050-1063
-void linear_f(const float* A, const float* B, float* out, size_t n, double a, double b, double x, hipStream_t stream)
-{
-    const float f = (a == b) ? 0 : ((x - a) / (b - a));
-    if (f == 0) copy_field(A, out, n, stream);
-    else if (f == 1) copy_field(B, out, n, stream);
-    else blend(A, B, out, n, f, stream);
-}
-
-// mifi_get_values_linear_conf_extrapol_f, :1085-1104
-void linear_conf_extrapol_f(float left, float right, const float* A, const float* B, float* out, size_t n, double a, double b, double x,
-                            hipStream_t stream)
-{
-    const float f = (a == b) ? 0 : ((x - a) / (b - a));
-    if (f == 0) copy_field(A, out, n, stream);
-    else if (f == 1) copy_field(B, out, n, stream);
-    else if ((f >= left) && (f <= right)) blend(A, B, out, n, f, stream);
-    else {
-        undefined_kernel<<<stream_blocks(n), kBlock, 0, stream>>>(out, n);
-        FA_HIP(hipGetLastError());
+    switch (cls) {
+    case blend_math::Class::CopyA: copy_field(A, out, n, stream); break;
+    case blend_math::Class::CopyB: copy_field(B, out, n, stream); break;
+    case blend_math::Class::Blend: blend_kernel<T><<<stream_blocks(n), kBlock, 0, stream>>>(A, B, out, n, f); break;
+    default:
+        if constexpr (std::is_same<T, float>::value) undefined_kernel<<<stream_blocks(n), kBlock, 0, stream>>>(out, n);  // no such branch in double
     }
+    FA_HIP(hipGetLastError());
 }
 
 }  // namespace
 
-// returns false where the reference returns MIFI_ERROR (non-positive coordinates of the log blends)
+// returns false where the reference returns MIFI_ERROR (non-positive coordinates of the log blends).  classify runs on the host:
+// the logarithms are taken by the same libm as the reference's.
 bool launch_get_values_1d_f(int kind, const float* A, const float* B, float* out, size_t n, double a, double b, double x, hipStream_t stream)
 {
-    switch (kind) {
-    case FIMEX_AMD_1D_NEAREST: if (n) copy_field(A, out, n, stream); return true;  // :1030-1034
-    case FIMEX_AMD_1D_LINEAR: if (n) linear_f(A, B, out, n, a, b, x, stream); return true;
-    case FIMEX_AMD_1D_LINEAR_WEAK_EXTRAPOL: if (n) linear_conf_extrapol_f(-1.f, 2.f, A, B, out, n, a, b, x, stream); return true;  // :1106-1109
-    case FIMEX_AMD_1D_LINEAR_NO_EXTRAPOL: if (n) linear_conf_extrapol_f(0.f, 1.f, A, B, out, n, a, b, x, stream); return true;     // :1110-1113
-    case FIMEX_AMD_1D_LINEAR_CONST_EXTRAPOL: {  // :1115-1126
-        const float f = (a == b) ? 0 : ((x - a) / (b - a));
-        if (n == 0) return true;
-        if (f >= 1) copy_field(B, out, n, stream);
-        else if (f <= 0) copy_field(A, out, n, stream);
-        else blend(A, B, out, n, f, stream);
-        return true;
-    }
-    case FIMEX_AMD_1D_LOG:  // :1134-1145; the three logarithms are taken on the host, by the same libm as the reference's
-        if (a <= 0 || b <= 0 || x <= 0) return false;
-        if (n) linear_f(A, B, out, n, std::log(a), std::log(b), std::log(x), stream);
-        return true;
-    case FIMEX_AMD_1D_LOG_LOG: {  // :1147-1156
-        if (a <= 0 || b <= 0 || x <= 0) return false;
-        const double la = std::log(a + M_E), lb = std::log(b + M_E), lx = std::log(x + M_E);
-        if (!(la <= 0 || lb <= 0 || lx <= 0) && n) linear_f(A, B, out, n, std::log(la), std::log(lb), std::log(lx), stream);
-        return true;  // the reference drops the inner status
-    }
-    default: throw Error("unknown 1-D blend " + std::to_string(kind));
-    }
+    if (!blend_math::kind_known(kind)) throw Error("unknown 1-D blend " + std::to_string(kind));
+    const blend_math::Blend c = blend_math::classify(kind, a, b, x);
+    // differs: the vertical kernels make the cell undefined; here the error is reported and nothing is written
+    if (c.cls == blend_math::Class::Error) return false;
+    if (n) blend_fields(c.cls, c.f, A, B, out, n, stream);
+    return true;
 }
 
 // mifi_get_values_linear_d, :1065-1083
 void launch_get_values_linear_d(const double* A, const double* B, double* out, size_t n, double a, double b, double x, hipStream_t stream)
 {
     if (n == 0) return;
-    const double f = (a == b) ? 0 : ((x - a) / (b - a));
-    if (f == 0) copy_field(A, out, n, stream);
-    else if (f == 1) copy_field(B, out, n, stream);
-    else blend(A, B, out, n, f, stream);
+    const blend_math::BlendOf<double> c = blend_math::classify_linear<double>(a, b, x);
+    blend_fields(c.cls, c.f, A, B, out, n, stream);
 }
 
 size_t cdm_type_size(int cdmType)

@@ -19,6 +19,7 @@
 #pragma once
 
 #include "backward_dispatch.hpp"
+#include "blend_math.hpp"
 #include "common.hpp"
 #include "staged_layout.hpp"
 
@@ -270,7 +271,7 @@ void launch_deaccumulate(const void* d_in, int cdmType, size_t n, size_t nt, siz
                          hipStream_t stream);
 
 // time_interpolate.hip: a series onto a new time axis (CDMTimeInterpolator); one entry per output step, worked out on the host
-enum class TimeStepClass : unsigned char { CopyA = 0, CopyB = 1, Blend = 2, Undefined = 3 };
+using TimeStepClass = blend_math::Class;  // of linear_weak_extrapol: CopyA, CopyB, Blend or Undefined
 struct TimeStep {
     uint32_t t1, t2;  // the pair of input slices
     float f;          // the blend factor of interpolation.c:1087
@@ -293,6 +294,9 @@ void launch_quality_mask(void* d_data, int dataType, size_t nData, const void* d
 // vertical.hip: vertical interpolation to fixed or template levels
 bool vertical_method_known(int method);
 void check_vertical_levels(const fimex_amd_vertical_levels* levels, const char* which, bool nonEmpty);  // throws: unknown kind, missing array
+// what the one-shot entries and the plan's create refuse alike; false: emptyIsDone and no cells, nothing has been asked beyond the levels
+bool check_vertical_search(int method, size_t nx, size_t ny, size_t nt, const fimex_amd_vertical_levels* inLevels,
+                           const fimex_amd_vertical_levels* outLevels, const double* level1, size_t nzo, bool emptyIsDone);
 void launch_vertical_interpolate(int method, size_t nx, size_t ny, size_t nt, const float* d_in, const fimex_amd_vertical_levels& inLevels,
                                  const fimex_amd_vertical_levels* outLevels, const double* h_level1, size_t nzo, const double* d_validMin,
                                  const double* d_validMax, float clampMin, float clampMax, float* d_out, hipStream_t stream);

@@ -66,12 +66,12 @@ __device__ __forceinline__ void walk(const T* __restrict__ in, float* __restrict
         }
         const float f = sb.f[s];
         Floats<V> y;
-        switch ((TimeStepClass)sb.cls[s]) {
+        switch ((TimeStepClass)sb.cls[s]) {  // wave-uniform: a scalar branch around the vector loops
         case TimeStepClass::CopyA: y = A; break;  // the reference's memcpy: no 0 * NaN from the other slice (:1088-1093)
         case TimeStepClass::CopyB: y = B; break;
         case TimeStepClass::Blend:
 #pragma unroll
-            for (int e = 0; e < V; ++e) y.v[e] = A.v[e] + f * (B.v[e] - A.v[e]);  // :1045
+            for (int e = 0; e < V; ++e) y.v[e] = blend_math::value(TimeStepClass::Blend, f, A.v[e], B.v[e]);  // :1045
             break;
         default:
 #pragma unroll

@@ -2,7 +2,8 @@
 // CDMVerticalInterpolator::getLevelDataSlice, src/CDMVerticalInterpolator.cc:441-504, restated per column.
 //
 // A lane owns one column; consecutive lanes own x-adjacent columns, so every load of a level plane, a data plane or ps is
-// coalesced along x.  In a column whose levels are strictly monotonic the pair of input levels around a target comes from a
+// coalesced along x.  The search (vertical_search.hpp) is what vertical_plan.hip shares; the factor and the log coordinates
+// of the blend are blend_math.hpp's.  In a column whose levels are strictly monotonic the pair of input levels around a target comes from a
 // bisection (monotonic_pair); otherwise, and wherever the bisection cannot be sure, from the reference's walk: output levels
 // go in groups of kGroup and the scan of include/fimex/Utils.h:251-290 runs once over the column's input levels for the whole
 // group, with its state (lowDiff, highDiff, lowest, highest per output level) in registers.  Levels given by a formula are recomputed from ps in every pass (two FP64 operations, no memory), an explicit
@@ -189,6 +190,24 @@ void check_vertical_levels(const fimex_amd_vertical_levels* l, const char* which
 
 bool vertical_method_known(int method) { return method >= FIMEX_AMD_VINT_METHOD_LIN && method <= FIMEX_AMD_VINT_METHOD_LIN_CONST_EXTRA; }
 
+bool check_vertical_search(int method, size_t nx, size_t ny, size_t nt, const fimex_amd_vertical_levels* inLevels,
+                           const fimex_amd_vertical_levels* outLevels, const double* level1, size_t nzo, bool emptyIsDone)
+{
+    FA_REQUIRE(vertical_method_known(method), "unknown vertical interpolation method " + std::to_string(method));
+    const bool nonEmpty = nx * ny * nt > 0;
+    check_vertical_levels(inLevels, "input", nonEmpty);
+    if (outLevels) {
+        check_vertical_levels(outLevels, "template", nonEmpty);
+        FA_REQUIRE(outLevels->nz == nzo, "nzo differs from the template's number of levels");
+    }
+    // differs: on an empty grid the one-shot entries have nothing to do and ask no more; the plan's create asks regardless
+    if (emptyIsDone && !nonEmpty) return false;
+    FA_REQUIRE(outLevels != nullptr || level1 != nullptr, "fixed levels need level1[nzo]");
+    FA_REQUIRE(inLevels->nz > 0, "no input levels (nzi == 0)");
+    FA_REQUIRE(nzo > 0, "no output levels (nzo == 0)");
+    return true;
+}
+
 // every argument has been checked (capi.hip); the pointers in the two descriptions are device pointers except the coefficients
 void launch_vertical_interpolate(int method, size_t nx, size_t ny, size_t nt, const float* d_in, const fimex_amd_vertical_levels& inLevels,
                                  const fimex_amd_vertical_levels* outLevels, const double* h_level1, size_t nzo, const double* d_validMin,
@@ -197,29 +216,14 @@ void launch_vertical_interpolate(int method, size_t nx, size_t ny, size_t nt, co
     const size_t plane = nx * ny;
     if (plane == 0 || nt == 0 || nzo == 0) return;
     const dim3 grid = column_grid(plane, nt);
-    StreamScratch scratch(coefficient_count(inLevels) + (outLevels ? coefficient_count(*outLevels) : nzo), stream);
+    StreamScratch scratch(search_scratch_doubles(inLevels, outLevels, nzo), stream);
     VintArgs a{};
-    a.in = device_levels(inLevels, scratch, stream);
-    if (outLevels) a.out = device_levels(*outLevels, scratch, stream);
-    else {
-        a.out.kind = -1;
-        double* l1 = scratch.take(nzo);
-        upload(l1, h_level1, nzo, stream);
-        a.level1 = l1;
-    }
-    a.validMin = d_validMin;
-    a.validMax = d_validMax;
+    fill_search_args(a, method, inLevels, outLevels, h_level1, nzo, d_validMin, d_validMax, plane, scratch, stream);
     a.data = d_in;
     a.result = d_out;
-    a.plane = plane;
-    a.nzo = (unsigned)nzo;
-    a.method = method;
     a.clampMin = clampMin;
     a.clampMax = clampMax;
-    a.bisect = tuning("VERTICAL_BISECT", 1);
-    // output levels per walk of a column, measured: 4 is faster than 8, whose registers leave 2 waves per SIMD
-    if (tuning("VERTICAL_GROUP", 4) == 8) vertical_kernel<8><<<grid, kBlock, 0, stream>>>(a);
-    else vertical_kernel<4><<<grid, kBlock, 0, stream>>>(a);
+    for_search_group([&](auto group) { vertical_kernel<decltype(group)::value><<<grid, kBlock, 0, stream>>>(a); });
     FA_HIP(hipGetLastError());
 }
 

@@ -1,7 +1,8 @@
-// What vertical.hip (interpolation) and vertical_levels.hip (the level converters, n6) share: the device-side form
-// of fimex_amd_vertical_levels with the levels of one column, the upload of host coefficient arrays as kernel arguments into
-// stream-ordered scratch, and the launch grid of a lane per column.  Everything has internal linkage: each of the two files
-// compiles its own copy, as the code was when it lived in vertical.hip alone.
+// What the vertical files share -- vertical.hip and vertical_plan.hip (interpolation; through
+// vertical_search.hpp), vertical_levels.hip (the level converters, n6) and vertical_velocity.hip: the device-side form of
+// fimex_amd_vertical_levels with the levels of one column, the upload of host coefficient arrays as kernel arguments into
+// stream-ordered scratch, and the launch grid of a lane per column.  Everything has internal linkage: every file that includes
+// it compiles its own copy of the upload kernel and the host helpers.  Column also compiles for the host (vertical_search.hpp).
 #pragma once
 #include "plan.hpp"
 
@@ -32,7 +33,7 @@ struct Column {
     const float* fieldCol;  // FIELD: &field[t][0][cell]
     size_t plane;
     double ps, pDiff;
-    __device__ Column(const Levels& L, size_t t, size_t cell, size_t plane) : L(L), fieldCol(nullptr), plane(plane), ps(0), pDiff(0)
+    __host__ __device__ Column(const Levels& L, size_t t, size_t cell, size_t plane) : L(L), fieldCol(nullptr), plane(plane), ps(0), pDiff(0)
     {
         if (L.kind == FIMEX_AMD_VLEVEL_FIELD) fieldCol = L.field + t * L.nz * plane + cell;
         else if (L.kind != FIMEX_AMD_VLEVEL_AXIS) {
@@ -40,7 +41,7 @@ struct Column {
             pDiff = ps - L.ptop;  // vertical_coordinate_transformations.c:39
         }
     }
-    __device__ float level(unsigned k) const
+    __host__ __device__ float level(unsigned k) const
     {
         switch (L.kind) {
         case FIMEX_AMD_VLEVEL_FIELD: return fieldCol[(size_t)k * plane];

@@ -1,8 +1,9 @@
 // Vertical interpolation in two halves: a plan that holds the search of vertical.hip, and an apply that only
 // gathers two values per output cell, blends, clamps and stores -- on the variable's stored type, for several variables at once.
 //
-// Build: vertical_kernel's shape (a lane per column, output levels in groups of kGroup, bisection or the reference's walk from
-// vertical_search.hpp), storing the pair and the folded factor of every output cell instead of gathering data.
+// Build: vertical_kernel's shape and search (vertical_search.hpp: a lane per column, output levels in groups of kGroup,
+// bisection or the reference's walk), storing the pair and the folded factor (blend_math.hpp) of every output cell instead of
+// gathering data.
 //
 // Apply: a workgroup owns kBlock groups of 16 bytes of output along x and walks the output levels, so that the lines of an input
 // plane it has just read are still in L2 when the next level comes back to them.  Per group a lane loads its entries (16-byte
@@ -195,7 +196,7 @@ __device__ __forceinline__ void apply_cells(const ApplyArgs<T, NV>& a, size_t t,
         Pack<T, V> o;
 #pragma unroll
         for (int c = 0; c < V; ++c) {
-            float y = (f[c] == 0) ? A[c] : (f[c] == 1) ? B[c] : A[c] + f[c] * (B[c] - A[c]);
+            float y = FA_BM_VALUE_OF_FOLDED(f[c], A[c], B[c]);  // blend_math.hpp
             if ((pr[c] & 0xffffu) == (pr[c] >> 16)) y = undefined_f();
             // src/CDMVerticalInterpolator.cc:494-504 (a NaN bound compares false, as the reference's isnan() test skips it)
             if (y < a.clampMin[v]) y = a.clampMin[v];
@@ -264,27 +265,12 @@ void build_vertical_plan(fimex_amd_vertical_plan& plan, const fimex_amd_vertical
     const size_t plane = plan.info.nx * plan.info.ny, nt = plan.info.nt, nzo = plan.info.nzo;
     if (plane * nt > 0) {
         const dim3 grid = column_grid(plane, nt);
-        StreamScratch scratch(coefficient_count(inLevels) + (outLevels ? coefficient_count(*outLevels) : nzo), stream);
+        StreamScratch scratch(search_scratch_doubles(inLevels, outLevels, nzo), stream);
         PlanArgs a{};
-        a.in = device_levels(inLevels, scratch, stream);
-        if (outLevels) a.out = device_levels(*outLevels, scratch, stream);
-        else {
-            a.out.kind = -1;
-            double* l1 = scratch.take(nzo);
-            upload(l1, h_level1, nzo, stream);
-            a.level1 = l1;
-        }
-        a.validMin = d_validMin;
-        a.validMax = d_validMax;
+        fill_search_args(a, plan.info.method, inLevels, outLevels, h_level1, nzo, d_validMin, d_validMax, plane, scratch, stream);
         a.pair = plan.pair.get();
         a.factor = plan.factor.get();
-        a.plane = plane;
-        a.nzo = (unsigned)nzo;
-        a.method = plan.info.method;
-        a.bisect = tuning("VERTICAL_BISECT", 1);
-        // the group of vertical_kernel, by the same switch
-        if (tuning("VERTICAL_GROUP", 4) == 8) plan_build_kernel<8><<<grid, kBlock, 0, stream>>>(a);
-        else plan_build_kernel<4><<<grid, kBlock, 0, stream>>>(a);
+        for_search_group([&](auto group) { plan_build_kernel<decltype(group)::value><<<grid, kBlock, 0, stream>>>(a); });
         FA_HIP(hipGetLastError());
     }
     FA_HIP(hipEventRecord(plan.built.e, stream));

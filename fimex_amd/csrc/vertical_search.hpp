@@ -1,7 +1,12 @@
 // What vertical.hip (the one-shot interpolation) and vertical_plan.hip (the same search stored as a plan) share: the
-// search for the pair of input levels around a target, by bisection or by the reference's walk, and the factor expressions of the
-// blends.  One statement of each, so that a plan followed by its apply gives the bits of the one-shot kernel.  Everything has
-// internal linkage, as in vertical_common.hpp: each of the two files compiles its own copy.
+// search for the pair of input levels around a target, by bisection (monotonic_pair) or by the reference's walk (walk_pairs), and
+// the host code that fills the search's arguments and picks the group size.  One statement of each, so that a plan followed by its
+// apply gives the bits of the one-shot kernel.  The factor and the log coordinates of the blends are blend_math.hpp's; the three
+// functions below give them the names the two kernels use.  The kernels keep their own copy of the loop around the search: on shared
+// functions (the monotonicity scan, the group loop) they came out as other machine code, and they are to stay the code that was
+// measured (profiles/vertical_blend_resource_usage.md).  monotonic_pair, walk_pairs and Column also compile for the host:
+// tests/vertical_search_host.hip runs them on the CPU against the reference's sequential search.  Everything has internal linkage,
+// as in vertical_common.hpp.
 #pragma once
 #include "vertical_common.hpp"
 
@@ -12,30 +17,9 @@ namespace fimex_amd {
 
 namespace {
 
-// the f of mifi_get_values_linear_f and its kin with n = 1, src/interpolation.c:1049, :1087, :1117
-__device__ inline float linear_factor(double a, double b, double x) { return (a == b) ? 0 : ((x - a) / (b - a)); }
-
-// the coordinates of mifi_get_values_log_f, :1131-1142; false: MIFI_ERROR
-__device__ inline bool log_coordinates(double& a, double& b, double& x)
-{
-    if (a <= 0 || b <= 0 || x <= 0) return false;
-    a = log(a);
-    b = log(b);
-    x = log(x);
-    return true;
-}
-
-// the coordinates of mifi_get_values_log_log_f, :1144-1156; false: MIFI_ERROR
-__device__ inline bool loglog_coordinates(double& a, double& b, double& x)
-{
-    if (a <= 0 || b <= 0 || x <= 0) return false;
-    const double la = log(a + M_E), lb = log(b + M_E), lx = log(x + M_E);
-    if (la <= 0 || lb <= 0 || lx <= 0) return false;
-    a = log(la);
-    b = log(lb);
-    x = log(lx);
-    return true;
-}
+__device__ inline float linear_factor(double a, double b, double x) { return blend_math::factor<float>(a, b, x); }
+__device__ inline bool log_coordinates(double& a, double& b, double& x) { return blend_math::log_coordinates(a, b, x); }
+__device__ inline bool loglog_coordinates(double& a, double& b, double& x) { return blend_math::loglog_coordinates(a, b, x); }
 
 // The pair find_closest_neighbor_distinct_elements returns for a column whose levels are strictly increasing (mono > 0) or
 // strictly decreasing (mono < 0), found by bisection instead of the walk.  In such a column the differences the walk compares
@@ -47,7 +31,7 @@ __device__ inline bool loglog_coordinates(double& a, double& b, double& x)
 //   at 0 (Utils.h:263-268).  Decreasing: (q, q - 1) with q = n - cnt.  Beyond the end the column is walked TOWARDS, the fallback
 //   (Utils.h:204-236) ends on (n - 1, n - 2); beyond the end it starts from, it never finds a second level: (0, 0).
 // returns first | second << 16, or -1 where the walk has to decide
-__device__ __noinline__ int monotonic_pair(const Column& in, int n, int mono, double x)
+__host__ __device__ __noinline__ int monotonic_pair(const Column& in, int n, int mono, double x)
 {
     if (mono == 0 || !(x == x) || n > 0x7fff) return -1;
     int lo = 0, hi = n;
@@ -87,7 +71,7 @@ __device__ __noinline__ int monotonic_pair(const Column& in, int n, int mono, do
 // find_closest_neighbor_distinct_elements (Utils.h:251-290) with its fallback find_closest_distinct_elements (:204-236) for
 // kGroup values of x in one walk over the column (a second one where a value extrapolates), every comparison as written
 template <int kGroup>
-__device__ inline void walk_pairs(const Column& in, unsigned nzi, const double (&x)[kGroup], unsigned (&first)[kGroup], unsigned (&second)[kGroup])
+__host__ __device__ inline void walk_pairs(const Column& in, unsigned nzi, const double (&x)[kGroup], unsigned (&first)[kGroup], unsigned (&second)[kGroup])
 {
     const double maxDiff = DBL_MAX;
     double lowDiff[kGroup], highDiff[kGroup];
@@ -152,6 +136,47 @@ __device__ inline void walk_pairs(const Column& in, unsigned nzi, const double (
 #pragma unroll
     for (int g = 0; g < kGroup; ++g)
         if (need[g]) { first[g] = r1[g]; second[g] = r2[g]; }
+}
+
+// ---- host: the arguments and the group size, for both kernels (VintArgs and PlanArgs name the search's fields alike)
+
+// doubles of scratch that fill_search_args takes
+size_t search_scratch_doubles(const fimex_amd_vertical_levels& inLevels, const fimex_amd_vertical_levels* outLevels, size_t nzo)
+{
+    return coefficient_count(inLevels) + (outLevels ? coefficient_count(*outLevels) : nzo);
+}
+
+// Fills the search's fields of a kernel's arguments from the two level descriptions (the pointers in them are device pointers except the coefficients, which
+// go up with h_level1 into scratch of search_scratch_doubles: the caller owns it, it has to outlive the launch).
+// outLevels == NULL: fixed levels.
+template <class Args>
+void fill_search_args(Args& a, int method, const fimex_amd_vertical_levels& inLevels, const fimex_amd_vertical_levels* outLevels,
+                      const double* h_level1, size_t nzo, const double* d_validMin, const double* d_validMax, size_t plane,
+                      StreamScratch& scratch, hipStream_t stream)
+{
+    a.in = device_levels(inLevels, scratch, stream);
+    if (outLevels) a.out = device_levels(*outLevels, scratch, stream);
+    else {
+        a.out.kind = -1;
+        double* l1 = scratch.take(nzo);
+        upload(l1, h_level1, nzo, stream);
+        a.level1 = l1;
+    }
+    a.validMin = d_validMin;
+    a.validMax = d_validMax;
+    a.plane = plane;
+    a.nzo = (unsigned)nzo;
+    a.method = method;
+    a.bisect = tuning("VERTICAL_BISECT", 1);
+}
+
+// f(std::integral_constant<int, kGroup>): output levels per walk of a column, measured: 4 is faster than 8,
+// whose registers leave 2 waves per SIMD
+template <class F>
+void for_search_group(F&& f)
+{
+    if (tuning("VERTICAL_GROUP", 4) == 8) f(std::integral_constant<int, 8>{});
+    else f(std::integral_constant<int, 4>{});
 }
 
 }  // namespace

@@ -913,6 +913,30 @@ def test_blend_device_in_place_and_double(fa):
     assert cases.same(fA.cpu().numpy(), want)
 
 
+@pytest.mark.parametrize("alias", ["A", "B"])
+@pytest.mark.parametrize("kind", range(7))
+def test_blend_device_output_aliases_an_input(fa, kind, alias):
+    """Every kind with out == A and with out == B, on each branch its factor can select: a copy onto itself is no copy, a copy of
+    the other field, the blend and the undefined fill each read a cell before they write it.  1001 floats: four workgroups."""
+    import torch
+    A = cases.field(1, 7, 143, seed=kind + 3, nan_frac=0.05).reshape(-1)
+    B = cases.field(1, 7, 143, seed=kind + 60, nan_frac=0.05).reshape(-1)
+    for a, b, x in ((2., 5., 3.), (2., 5., 2.), (2., 5., 5.), (2., 5., 20.), (2., 5., -0.5), (5., 5., 1.)):
+        want, rc = oracle.get_values_1d(kind, A, B, a, b, x)
+        tA, tB = torch.from_numpy(A).cuda(), torch.from_numpy(B).cuda()
+        out = tA if alias == "A" else tB
+        if rc != oracle.OK:  # the log kinds at x = -0.5: refused, nothing written
+            with pytest.raises(fa.FimexAmdError):
+                fa.get_values_1d_device(kind, tA.data_ptr(), tB.data_ptr(), out.data_ptr(), A.size, a, b, x)
+            want = A if alias == "A" else B
+        else:
+            fa.get_values_1d_device(kind, tA.data_ptr(), tB.data_ptr(), out.data_ptr(), A.size, a, b, x)
+        torch.cuda.synchronize()
+        assert cases.same(out.cpu().numpy(), want), (a, b, x, cases.describe_mismatch(out.cpu().numpy(), want))
+        other, was = (tB, B) if alias == "A" else (tA, A)
+        assert np.array_equal(other.cpu().numpy().view(np.uint32), was.view(np.uint32)), "the other input changed"
+
+
 # ---------------------------------------------------------------- coordinate-based nearest neighbour plans (SURVEY 8f n3)
 from test_oracle_props import _curvilinear_grid, _great_circle_cos
 

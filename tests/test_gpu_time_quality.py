@@ -148,6 +148,20 @@ def test_time_capped_grid_and_forced_split(fa, tuning_build, monkeypatch, split)
         _check_time(_run_time(fa, x, old, new), x, old, new, (split, code, n))
 
 
+def test_time_every_branch_on_either_side_of_a_chunk_boundary(fa):
+    """Copy A, copy B, blend and undefined in turn, 80 steps: every branch inside one launch, and the 32-step chunk boundaries of the
+    split launch (few cells: the product library splits) have all four within two steps on either side."""
+    old = tq.OLD_TIMES
+    new = np.tile([0.0, 6.0, 3.0, -100.0], 20)
+    t1, t2 = tq.time_mapping(old, new)
+    branch = [tq.blend_factor(old[int(a)], old[int(b)], x)[1] for a, b, x in zip(t1, t2, new)]
+    for edge in (fa.TIME_CHUNK_STEPS, 2 * fa.TIME_CHUNK_STEPS):
+        assert set(branch[edge - 2:edge + 2]) == {tq.COPY_A, tq.COPY_B, tq.BLEND, tq.UNDEFINED}
+    for code, n in ((tq.CDM_FLOAT, 67), (tq.CDM_SHORT, 68), (tq.CDM_DOUBLE, 300)):
+        x = tq.series(500 + code, tq.DTYPES[code], old.size, n)
+        _check_time(_run_time(fa, x, old, new), x, old, new, (code, n))
+
+
 def test_time_equals_the_chain_of_pair_blends(fa):
     """Bit for bit, NaN included, with one fimex_amd_get_values_1d_f_device(LINEAR_WEAK_EXTRAPOL) call per output step on float input."""
     import torch

@@ -20,6 +20,7 @@ import vertical_ref as vr
 pytestmark = pytest.mark.gpu
 
 P0 = 1000.0
+BLOCK = 256  # columns per workgroup (kBlock, csrc/common.hpp)
 PS_CLASSES = np.array([955.0, 985.5, 1003.0, 1041.0], np.float32)
 
 
@@ -429,6 +430,60 @@ def test_bisection_and_walk_give_the_same_bits(fa, tuning_build, monkeypatch, ki
             per_level = [int(np.count_nonzero(~_same_cells(got[:, k], want[:, k]))) for k in range(nzo)]
             wrong.append((bisect, group, per_level))
     assert not wrong, wrong
+
+
+@pytest.mark.parametrize("group", [4, 8])
+@pytest.mark.parametrize("nzo", [1, 3, 4, 5, 9])
+def test_short_last_groups(fa, tuning_build, monkeypatch, nzo, group):
+    """Output level counts below, at and above the group sizes: a short last group of 4 and of 8 (tuning build) stores its own
+    levels only, each with its own value."""
+    monkeypatch.setenv("FIMEX_AMD_VERTICAL_GROUP", str(group))
+    data, inL, _, level1 = make_case(70 + nzo, vr.FIELD, None, 31, 9, 2, 7, nzo, "inc", False)
+    got = fa.vertical_interpolate_host(vr.LIN, data, _fa_levels(fa, inL), None, level1)
+    _compare(vr.LIN, got, *_want(vr.LIN, data, inL, None, level1))
+
+
+def mixed_columns(seed, nx, ny, nt, nzi, nzo):
+    """make_case on a level field whose columns alternate along x between strictly increasing levels (the bisection) and levels with
+    repeats (the walk): both kinds sit in every wave."""
+    data, incL, _, level1 = make_case(seed, vr.FIELD, None, nx, ny, nt, nzi, nzo, "inc", False)
+    _, repL, _, _ = make_case(seed + 1, vr.FIELD, None, nx, ny, nt, nzi, nzo, "rep", False)
+    inc, rep = incL.field.reshape(nt, nzi, ny, nx), repL.field.reshape(nt, nzi, ny, nx)
+    field = np.where((np.arange(nx) % 2 == 0)[None, None, None, :], inc, rep)
+    mono = np.all(np.diff(field, axis=1) > 0, axis=1)  # make_case puts a level on a target in some columns: not every even one
+    assert mono[..., 0::2].mean() > 0.5 and not mono[..., 1::2].any()
+    for t in range(nt):
+        waves = mono[t].reshape(-1)[:(nx * ny) // 64 * 64].reshape(-1, 64)
+        assert np.all(waves.any(axis=1) & ~waves.all(axis=1))
+    return data, vr.Levels(vr.FIELD, nzi, field=field), level1
+
+
+@pytest.mark.parametrize("method", vr.LINEAR_FAMILY)
+def test_bisecting_and_walking_columns_in_one_wave(fa, method):
+    data, inL, level1 = mixed_columns(80, 53, 37, 2, 7, 11)
+    got = fa.vertical_interpolate_host(method, data, _fa_levels(fa, inL), None, level1)
+    _compare(method, got, *_want(method, data, inL, None, level1))
+
+
+@pytest.mark.parametrize("plane", [BLOCK - 1, BLOCK, BLOCK + 1])
+def test_planes_around_a_workgroup(fa, plane):
+    """One column less than a workgroup's, exactly its columns and one more, two positions of the unlimited dimension: the output
+    on the device between guard bytes."""
+    import torch
+    nt, nzi, nzo = 2, 7, 5
+    data, inL, _, level1 = make_case(90 + plane, vr.HYBRID_SIGMA, None, plane, 1, nt, nzi, nzo, "dec", False)
+    want = _want(vr.LIN_WEAK_EXTRA, data, inL, None, level1)[0]
+    li = _fa_levels(fa, inL, device=True)
+    d_in = torch.from_numpy(data).cuda()
+    guard = 64
+    d_out = torch.full((guard + nt * nzo * plane + guard,), -7.0, dtype=torch.float32, device="cuda")
+    fa.vertical_interpolate_device(vr.LIN_WEAK_EXTRA, plane, 1, nt, d_in.data_ptr(), li, d_out.data_ptr() + 4 * guard, level1=level1,
+                                   stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    raw = d_out.cpu().numpy()
+    assert np.all(raw[:guard] == -7.0) and np.all(raw[-guard:] == -7.0), "wrote outside the output"
+    got = raw[guard:-guard].reshape(want.shape)
+    assert cases.same(got, want), cases.describe_mismatch(got, want)
 
 
 def test_errors(fa):

@@ -385,6 +385,34 @@ def test_bisection_and_walk_give_the_same_entries(fa, tuning_build, monkeypatch,
         _check_entries(vr.LIN, plan, ilev, x)
 
 
+@pytest.mark.parametrize("group", [4, 8])
+@pytest.mark.parametrize("nzo", [1, 3, 4, 5, 9])
+def test_short_last_groups_of_the_build(fa, tuning_build, monkeypatch, nzo, group):
+    """Output level counts below, at and above the group sizes: a short last group of 4 and of 8 (tuning build) stores its own entries
+    only."""
+    monkeypatch.setenv("FIMEX_AMD_VERTICAL_GROUP", str(group))
+    data, inL, _, level1 = tgv.make_case(70 + nzo, vr.FIELD, None, 31, 9, 2, 7, nzo, "inc", False)
+    plan = fa.VerticalPlan(vr.LIN, 31, 9, 2, tgv._fa_levels(fa, inL), None, level1)
+    _check_entries(vr.LIN, plan, *_levels_x(inL, None, level1, data.shape))
+    tgv._compare(vr.LIN, _float_apply(fa, plan, data), *tgv._want(vr.LIN, data, inL, None, level1))
+
+
+@pytest.mark.parametrize("method", vr.LINEAR_FAMILY)
+def test_bisecting_and_walking_columns_in_one_wave(fa, method):
+    data, inL, level1 = tgv.mixed_columns(80, 53, 37, 2, 7, 11)
+    plan, keep = _device_plan(fa, method, data.shape, inL, None, level1)
+    _check_entries(method, plan, *_levels_x(inL, None, level1, data.shape))
+    tgv._compare(method, _float_apply(fa, plan, data), *tgv._want(method, data, inL, None, level1))
+
+
+@pytest.mark.parametrize("plane", [tgv.BLOCK - 1, tgv.BLOCK, tgv.BLOCK + 1])
+def test_build_on_planes_around_a_workgroup(fa, plane):
+    data, inL, _, level1 = tgv.make_case(90 + plane, vr.HYBRID_SIGMA, None, plane, 1, 2, 7, 5, "dec", False)
+    plan, keep = _device_plan(fa, vr.LIN_WEAK_EXTRA, data.shape, inL, None, level1)
+    _check_entries(vr.LIN_WEAK_EXTRA, plan, *_levels_x(inL, None, level1, data.shape))
+    tgv._compare(vr.LIN_WEAK_EXTRA, _float_apply(fa, plan, data), *tgv._want(vr.LIN_WEAK_EXTRA, data, inL, None, level1))
+
+
 # ------------------------------------------------------------------ streams
 def test_a_side_stream_equals_the_host_forms(fa):
     import torch
