@@ -5,89 +5,31 @@
 // engines upload the previous one, the kernels run, and results flow back the same way in the other direction.
 #include "plan.hpp"
 
-#include <algorithm>
-#include <condition_variable>
-#include <cstring>
-#include <mutex>
-#include <thread>
-#include <vector>
+#include "hostpipe_layout.hpp"
 
 namespace fimex_amd {
 
+using namespace hostpipe;  // the ring's sizes and arithmetic, and the copier: hostpipe_layout.hpp
+
 namespace {
 
-constexpr size_t kPinBytes = (size_t)64 << 20;   // pinned staging per slot and direction
-constexpr size_t kDevFloatBytes = (size_t)128 << 20;  // float scratch per slot and direction (typed slices)
-constexpr int kSlots = 3;
-constexpr size_t kPiece = (size_t)8 << 20;            // a slot's transfer goes in pieces: host memcpy of one overlaps the DMA of the other
-constexpr int kPieces = (int)(kPinBytes / kPiece);
 constexpr int kMaxCached = 4;  // idle pipes kept for the next call
 constexpr int kMaxLive = 8;    // pipes in use at once: further callers wait for one (each pins up to 384 MB of host memory)
 
-// memcpy on several threads: the workers live as long as the pipe
-class ParallelCopier {
-public:
-    explicit ParallelCopier(int workers)
-    {
-        for (int i = 0; i < workers; ++i) threads_.emplace_back([this, i] { run(i); });
-    }
-    ~ParallelCopier()
-    {
-        { std::lock_guard<std::mutex> l(m_); stop_ = true; ++generation_; }
-        cv_.notify_all();
-        for (auto& t : threads_) t.join();
-    }
-    void copy(void* dst, const void* src, size_t bytes)
-    {
-        const size_t parts = threads_.size() + 1;
-        if (bytes < ((size_t)1 << 20) || threads_.empty()) { std::memcpy(dst, src, bytes); return; }
-        const size_t per = ((bytes + parts - 1) / parts + 4095) & ~(size_t)4095;
-        {
-            std::lock_guard<std::mutex> l(m_);
-            dst_ = static_cast<char*>(dst);
-            src_ = static_cast<const char*>(src);
-            bytes_ = bytes;
-            per_ = per;
-            pending_ = (int)threads_.size();
-            ++generation_;
-        }
-        cv_.notify_all();
-        part(threads_.size());  // the caller takes the last part
-        std::unique_lock<std::mutex> l(m_);
-        done_.wait(l, [this] { return pending_ == 0; });
-    }
-
-private:
-    void part(size_t k)
-    {
-        const size_t off = k * per_;
-        if (off < bytes_) std::memcpy(dst_ + off, src_ + off, std::min(per_, bytes_ - off));
-    }
-    void run(int k)
-    {
-        unsigned long long seen = 0;
-        for (;;) {
-            {
-                std::unique_lock<std::mutex> l(m_);
-                cv_.wait(l, [&] { return generation_ != seen; });
-                seen = generation_;
-                if (stop_) return;
-            }
-            part((size_t)k);
-            std::lock_guard<std::mutex> l(m_);
-            if (--pending_ == 0) done_.notify_one();
-        }
-    }
-    std::vector<std::thread> threads_;
-    std::mutex m_;
-    std::condition_variable cv_, done_;
-    unsigned long long generation_ = 0;
-    bool stop_ = false;
-    char* dst_ = nullptr;
-    const char* src_ = nullptr;
-    size_t bytes_ = 0, per_ = 0;
-    int pending_ = 0;
-};
+// the product build works with the constants of hostpipe_layout.hpp; the tuning build reads them per call, so that the tests reach
+// every branch of the ring with a few MB (FIMEX_AMD_HOST_SLOT_BYTES, _PIECE_BYTES, _FLOAT_BYTES, _STAGED_MIN_BYTES)
+RingSizes ring_sizes()
+{
+    RingSizes s;
+#ifdef FIMEX_AMD_TUNING
+    s.slotBytes = (size_t)tuning("HOST_SLOT_BYTES", (int)s.slotBytes);
+    s.pieceBytes = (size_t)tuning("HOST_PIECE_BYTES", (int)s.pieceBytes);
+    s.floatBytes = (size_t)tuning("HOST_FLOAT_BYTES", (int)s.floatBytes);
+    s.stagedCopyMin = (size_t)tuning("HOST_STAGED_MIN_BYTES", (int)s.stagedCopyMin);
+    if (const char* why = refuse(s)) throw Error(why);
+#endif
+    return s;
+}
 
 struct Slot {
     char *pinIn = nullptr, *pinOut = nullptr, *dRawIn = nullptr, *dRawOut = nullptr;
@@ -101,7 +43,7 @@ struct Slot {
 // raw buffers, only a conversion of stored types the float scratch (3 x 256 MB of HBM otherwise held for nothing).
 class HostPipe {
 public:
-    explicit HostPipe(int device) : device(device), copier(worker_count())
+    HostPipe(int device, const RingSizes& sizes) : device(device), sizes(sizes), copier(worker_count())
     {
         for (Slot& s : slots) {
             FA_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
@@ -127,12 +69,12 @@ public:
     enum Need { PinIn = 1, PinOut = 2, RawIn = 4, RawOut = 8, FloatIn = 16, FloatOut = 32 };
     void ensure(Slot& s, int need)
     {
-        if ((need & PinIn) && !s.pinIn) FA_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.pinIn), kPinBytes));
-        if ((need & PinOut) && !s.pinOut) FA_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.pinOut), kPinBytes));
-        if ((need & RawIn) && !s.dRawIn) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dRawIn), kPinBytes));
-        if ((need & RawOut) && !s.dRawOut) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dRawOut), kPinBytes));
-        if ((need & FloatIn) && !s.dFIn) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dFIn), kDevFloatBytes));
-        if ((need & FloatOut) && !s.dFOut) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dFOut), kDevFloatBytes));
+        if ((need & PinIn) && !s.pinIn) FA_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.pinIn), sizes.slotBytes));
+        if ((need & PinOut) && !s.pinOut) FA_HIP(hipHostMalloc(reinterpret_cast<void**>(&s.pinOut), sizes.slotBytes));
+        if ((need & RawIn) && !s.dRawIn) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dRawIn), sizes.slotBytes));
+        if ((need & RawOut) && !s.dRawOut) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dRawOut), sizes.slotBytes));
+        if ((need & FloatIn) && !s.dFIn) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dFIn), sizes.floatBytes));
+        if ((need & FloatOut) && !s.dFOut) FA_HIP(hipMalloc(reinterpret_cast<void**>(&s.dFOut), sizes.floatBytes));
     }
     static int worker_count()
     {
@@ -142,6 +84,7 @@ public:
         return (int)std::min(7u, std::max(1u, hw / 4));
     }
     int device;
+    RingSizes sizes;  // what the buffers were made for: a pipe serves calls with these sizes only
     Slot slots[kSlots];
     ParallelCopier copier;
 };
@@ -151,7 +94,7 @@ std::condition_variable g_poolFree;
 std::vector<HostPipe*> g_pool;
 int g_live = 0;  // pipes handed out
 
-HostPipe* acquire_pipe(int device)
+HostPipe* acquire_pipe(int device, const RingSizes& sizes)
 {
     {
         std::unique_lock<std::mutex> l(g_poolMutex);
@@ -159,14 +102,14 @@ HostPipe* acquire_pipe(int device)
         g_poolFree.wait(l, [] { return g_live < kMaxLive; });
         ++g_live;
         for (size_t i = 0; i < g_pool.size(); ++i)
-            if (g_pool[i]->device == device) {
+            if (g_pool[i]->device == device && g_pool[i]->sizes == sizes) {
                 HostPipe* p = g_pool[i];
                 g_pool.erase(g_pool.begin() + (long)i);
                 return p;
             }
     }
     try {
-        return new HostPipe(device);
+        return new HostPipe(device, sizes);
     } catch (...) {
         { std::lock_guard<std::mutex> l(g_poolMutex); --g_live; }
         g_poolFree.notify_one();
@@ -187,58 +130,59 @@ void release_pipe(HostPipe* p)
 }
 
 struct PipeLease {
-    explicit PipeLease(int device) : pipe(acquire_pipe(device)) {}
+    PipeLease(int device, const RingSizes& sizes) : pipe(acquire_pipe(device, sizes)) {}
     ~PipeLease() { release_pipe(pipe); }
     HostPipe* pipe;
 };
 
 }  // namespace
 
-// in / out: nz slices of inSliceBytes / outSliceBytes in caller memory.  fn(dRawIn, dRawOut, dFIn, dFOut, nzc, stream) turns
-// nzc uploaded slices into nzc result slices in dRawOut (dFIn / dFOut: float scratch of inSliceFloats / outSliceFloats per
+// in / out: nz slices of inSliceBytes / outSliceBytes in caller memory.  fn(dRawIn, dRawOut, dFIn, dFOut, n, stream) turns
+// n uploaded slices into n result slices in dRawOut (dFIn / dFOut: float scratch of inSliceFloats / outSliceFloats per
 // slice).  Returns false when a single slice does not fit the staging buffers (the caller takes the plain path).
 bool pipelined_slices(int device, const void* in, size_t inSliceBytes, void* out, size_t outSliceBytes, size_t inSliceFloats,
                       size_t outSliceFloats, size_t nz, const SliceChunkFn& fn)
 {
     if (tuning("HOST_PIPE", 1) == 0 || nz == 0) return false;
-    size_t nzc = std::min({kPinBytes / std::max<size_t>(inSliceBytes, 1), kPinBytes / std::max<size_t>(outSliceBytes, 1),
-                           kDevFloatBytes / std::max<size_t>(inSliceFloats * 4, 1), kDevFloatBytes / std::max<size_t>(outSliceFloats * 4, 1)});
-    if (nzc == 0) return false;
-    nzc = std::min(nzc, nz);
-    PipeLease lease(device);
+    const RingSizes sizes = ring_sizes();
+    const size_t fit = slices_per_chunk(slice_limits(sizes, inSliceBytes, outSliceBytes, inSliceFloats, outSliceFloats));
+    if (fit == 0) return false;
+    const Chunks chunks = slice_chunks(nz, fit);
+    PipeLease lease(device, sizes);
     HostPipe& p = *lease.pipe;
     const int need = HostPipe::PinIn | HostPipe::PinOut | HostPipe::RawIn | HostPipe::RawOut | (inSliceFloats ? HostPipe::FloatIn : 0) |
                      (outSliceFloats ? HostPipe::FloatOut : 0);
-    const size_t nChunks = (nz + nzc - 1) / nzc;
+    const size_t nChunks = chunks.count();
     for (size_t c = 0; c < std::min<size_t>(nChunks, kSlots); ++c) p.ensure(p.slots[c], need);
     const char* src = static_cast<const char*>(in);
     char* dst = static_cast<char*>(out);
-    auto count = [&](size_t c) { return std::min(nzc, nz - c * nzc); };
     auto finish = [&](size_t c) {  // piece by piece: the host copy of one piece overlaps the DMA of the next
-        Slot& s = p.slots[c % kSlots];
-        const size_t bytes = count(c) * outSliceBytes;
-        char* to = dst + c * nzc * outSliceBytes;
-        for (size_t off = 0, q = 0; off < bytes; off += kPiece, ++q) {
+        Slot& s = p.slots[slot_of(c, kSlots)];
+        const size_t bytes = chunks.units(c) * outSliceBytes;
+        char* to = dst + chunks.first(c) * outSliceBytes;
+        for (size_t q = 0, nq = piece_count(bytes, sizes.pieceBytes); q < nq; ++q) {
+            const Piece pc = piece_at(bytes, sizes.pieceBytes, q);
             FA_HIP(hipEventSynchronize(s.piece[q]));
-            p.copier.copy(to + off, s.pinOut + off, std::min(kPiece, bytes - off));
+            p.copier.copy(to + pc.off, s.pinOut + pc.off, pc.len);
         }
         FA_HIP(hipEventSynchronize(s.done));
     };
     size_t finished = 0;
     try {
-        for (size_t c = 0; c < nChunks; ++c) {
-            Slot& s = p.slots[c % kSlots];
-            if (c >= (size_t)kSlots) { finish(c - kSlots); finished = c - kSlots + 1; }
-            const size_t k = count(c), inBytes = k * inSliceBytes, outBytes = k * outSliceBytes;
-            const char* from = src + c * nzc * inSliceBytes;
-            for (size_t off = 0; off < inBytes; off += kPiece) {
-                const size_t len = std::min(kPiece, inBytes - off);
-                p.copier.copy(s.pinIn + off, from + off, len);
-                FA_HIP(hipMemcpyAsync(s.dRawIn + off, s.pinIn + off, len, hipMemcpyHostToDevice, s.stream));
+        for (size_t c = 0, drain = 0; c < nChunks; ++c) {
+            Slot& s = p.slots[slot_of(c, kSlots)];
+            if (drain_before(c, kSlots, &drain)) { finish(drain); finished = drain + 1; }
+            const size_t k = chunks.units(c), inBytes = k * inSliceBytes, outBytes = k * outSliceBytes;
+            const char* from = src + chunks.first(c) * inSliceBytes;
+            for (size_t q = 0, nq = piece_count(inBytes, sizes.pieceBytes); q < nq; ++q) {
+                const Piece pc = piece_at(inBytes, sizes.pieceBytes, q);
+                p.copier.copy(s.pinIn + pc.off, from + pc.off, pc.len);
+                FA_HIP(hipMemcpyAsync(s.dRawIn + pc.off, s.pinIn + pc.off, pc.len, hipMemcpyHostToDevice, s.stream));
             }
             fn(s.dRawIn, s.dRawOut, s.dFIn, s.dFOut, k, s.stream);
-            for (size_t off = 0, q = 0; off < outBytes; off += kPiece, ++q) {
-                FA_HIP(hipMemcpyAsync(s.pinOut + off, s.dRawOut + off, std::min(kPiece, outBytes - off), hipMemcpyDeviceToHost, s.stream));
+            for (size_t q = 0, nq = piece_count(outBytes, sizes.pieceBytes); q < nq; ++q) {
+                const Piece pc = piece_at(outBytes, sizes.pieceBytes, q);
+                FA_HIP(hipMemcpyAsync(s.pinOut + pc.off, s.dRawOut + pc.off, pc.len, hipMemcpyDeviceToHost, s.stream));
                 FA_HIP(hipEventRecord(s.piece[q], s.stream));
             }
             FA_HIP(hipEventRecord(s.done, s.stream));
@@ -251,30 +195,28 @@ bool pipelined_slices(int device, const void* in, size_t inSliceBytes, void* out
     return true;
 }
 
-namespace {
-constexpr size_t kStagedCopyMin = (size_t)16 << 20;  // below this a plain copy is as fast
-}
-
 // hipMemcpyAsync(HostToDevice) for caller-owned (pageable) memory: large copies go through the pinned ring with parallel
 // memcpy (about 2x the pageable rate) and have landed when this returns; small ones are enqueued on `stream` as before
 void host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t stream)
 {
     if (bytes == 0) return;
-    if (bytes < kStagedCopyMin || tuning("HOST_PIPE", 1) == 0) {
+    const RingSizes sizes = ring_sizes();
+    if (bytes < sizes.stagedCopyMin || tuning("HOST_PIPE", 1) == 0) {
         FA_HIP(hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, stream));
         return;
     }
     int device = 0;
     FA_HIP(hipGetDevice(&device));
-    PipeLease lease(device);
+    PipeLease lease(device, sizes);
     HostPipe& p = *lease.pipe;
-    const size_t nChunks = (bytes + kPinBytes - 1) / kPinBytes;
+    const Chunks chunks = byte_chunks(bytes, sizes);
+    const size_t nChunks = chunks.count();
     for (size_t c = 0; c < std::min<size_t>(nChunks, kSlots); ++c) p.ensure(p.slots[c], HostPipe::PinIn);
     try {
-        for (size_t c = 0; c < nChunks; ++c) {
-            Slot& s = p.slots[c % kSlots];
-            if (c >= (size_t)kSlots) FA_HIP(hipEventSynchronize(s.done));
-            const size_t off = c * kPinBytes, len = std::min(kPinBytes, bytes - off);
+        for (size_t c = 0, drain = 0; c < nChunks; ++c) {
+            Slot& s = p.slots[slot_of(c, kSlots)];
+            if (drain_before(c, kSlots, &drain)) FA_HIP(hipEventSynchronize(p.slots[slot_of(drain, kSlots)].done));
+            const size_t off = chunks.first(c), len = chunks.units(c);
             p.copier.copy(s.pinIn, static_cast<const char*>(h_src) + off, len);
             FA_HIP(hipMemcpyAsync(static_cast<char*>(d_dst) + off, s.pinIn, len, hipMemcpyHostToDevice, s.stream));
             FA_HIP(hipEventRecord(s.done, s.stream));
@@ -290,30 +232,30 @@ void host_to_device(void* d_dst, const void* h_src, size_t bytes, hipStream_t st
 void device_to_host(void* h_dst, const void* d_src, size_t bytes, hipStream_t stream)
 {
     if (bytes == 0) return;
-    if (bytes < kStagedCopyMin || tuning("HOST_PIPE", 1) == 0) {
+    const RingSizes sizes = ring_sizes();
+    if (bytes < sizes.stagedCopyMin || tuning("HOST_PIPE", 1) == 0) {
         FA_HIP(hipMemcpyAsync(h_dst, d_src, bytes, hipMemcpyDeviceToHost, stream));
         return;
     }
     FA_HIP(hipStreamSynchronize(stream));
     int device = 0;
     FA_HIP(hipGetDevice(&device));
-    PipeLease lease(device);
+    PipeLease lease(device, sizes);
     HostPipe& p = *lease.pipe;
-    const size_t nChunks = (bytes + kPinBytes - 1) / kPinBytes;
+    const Chunks chunks = byte_chunks(bytes, sizes);
+    const size_t nChunks = chunks.count();
     for (size_t c = 0; c < std::min<size_t>(nChunks, kSlots); ++c) p.ensure(p.slots[c], HostPipe::PinOut);
     auto finish = [&](size_t c) {
-        Slot& s = p.slots[c % kSlots];
+        Slot& s = p.slots[slot_of(c, kSlots)];
         FA_HIP(hipEventSynchronize(s.done));
-        const size_t off = c * kPinBytes;
-        p.copier.copy(static_cast<char*>(h_dst) + off, s.pinOut, std::min(kPinBytes, bytes - off));
+        p.copier.copy(static_cast<char*>(h_dst) + chunks.first(c), s.pinOut, chunks.units(c));
     };
     size_t finished = 0;
     try {
-        for (size_t c = 0; c < nChunks; ++c) {
-            Slot& s = p.slots[c % kSlots];
-            if (c >= (size_t)kSlots) { finish(c - kSlots); finished = c - kSlots + 1; }
-            const size_t off = c * kPinBytes;
-            FA_HIP(hipMemcpyAsync(s.pinOut, static_cast<const char*>(d_src) + off, std::min(kPinBytes, bytes - off), hipMemcpyDeviceToHost, s.stream));
+        for (size_t c = 0, drain = 0; c < nChunks; ++c) {
+            Slot& s = p.slots[slot_of(c, kSlots)];
+            if (drain_before(c, kSlots, &drain)) { finish(drain); finished = drain + 1; }
+            FA_HIP(hipMemcpyAsync(s.pinOut, static_cast<const char*>(d_src) + chunks.first(c), chunks.units(c), hipMemcpyDeviceToHost, s.stream));
             FA_HIP(hipEventRecord(s.done, s.stream));
         }
         for (size_t c = finished; c < nChunks; ++c) finish(c);

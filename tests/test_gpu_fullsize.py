@@ -182,7 +182,8 @@ def test_host_calls_with_slices_beyond_the_staging_buffers(fa):
     w16 = oracle.interpolation_array2data(oracle.interpolate_values(oracle.BILINEAR, px, py, oracle.data2interpolation_array(s16, -32767.0),
                                                                     inX, inY, outX, outY, nthreads=16), oracle.CDM_SHORT, -32767.0)
     assert np.array_equal(got16, w16.reshape(got16.shape))
-    # 11 slices of 22 MB: chunks of two slices, six chunks through three slots
+    # 11 slices of 22 080 000 bytes: three fit a 64 MiB slot, so four chunks (3, 3, 3, 2 slices) through three slots
+    # (tests/test_hostpipe_layout.py::test_the_chunks_of_the_full_size_case pins these counts)
     inX, inY = 2400, 2300
     px, py = cases.backward_positions(inX, inY, outX, outY, seed=10)
     f = rng.normal(0, 1, (11, inY, inX)).astype(np.float32)
